@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- AMG-PCG solve throughput on the headline workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): 3-D 7-point FD Poisson on the unit cube, 256^3
 interior points (16 777 216 DOF, 117 047 296 nnz), rhs from the reference's generator,
@@ -10,6 +10,13 @@ V(1,1).  One "step" = one complete fasp_solver_dcsr_krylo
 Krylov solve (all PCG iterations, every V-cycle, the coarse-level safe CG) on the
 resident hierarchy, with b and x already in HBM.  The host-side AMG setup and the
 upload happen once, before the warm-up, and are reported separately.
+
+A plain run sets up, warms up, times the K steps and prints the line: value, ms_per_step and the
+level-0 roofline entry taken from those same steps.  Everything below that needs runs of its own
+(roofline_plain_csr, ceilings, parity_reference, cpu_baseline, variable_coefficient, other_configs;
+with N > 1 also the CPU baseline, the diagnostic solve, the parity entry and the 512^3 leg) is
+measured with --full only; the --no-* options switch single parts of --full off.
+--dump-outputs DIR writes what the last timed step returned as float64 .npy files (dump_outputs()).
 
 value    = DOF / s = (rows x K) / (time of K solves), whole job (all ranks)
 roofline = the level-0 SpMV kernel the solve runs (t = A p fused with the (t,p) partial
@@ -316,6 +323,23 @@ def roofline_entry(kind, moved_bytes, kernel_ms, launches, note=None, workload=N
     return out
 
 
+DUMP_ROWS = 1 << 21   # entries of x that --dump-outputs writes (16 MiB; every row of a smaller solution)
+
+
+def dump_outputs(d, x, hist, iterations, relres):
+    """--dump-outputs DIR: what the last timed step returned, as float64 .npy files (32 MiB at most in all):
+    x.npy = the solution at the rows in x_rows.npy (every row up to DUMP_ROWS, else a fixed, seeded sample of rows),
+    residual_history.npy = the solver's residual history, solve_status.npy = (iterations, relres)."""
+    os.makedirs(d, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    rows = np.arange(x.size) if x.size <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(x.size, DUMP_ROWS, replace=False))
+    np.save(os.path.join(d, "x.npy"), x[rows])
+    np.save(os.path.join(d, "x_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "residual_history.npy"), np.asarray(hist, dtype=np.float64))
+    np.save(os.path.join(d, "solve_status.npy"), np.array([iterations, relres], dtype=np.float64))
+    log(f"outputs of the last timed step written to {d}")
+
+
 def spawn_ranks(args):
     """--gpus N without a launcher: start the ranks as a child job (never re-exec this process)."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -324,6 +348,10 @@ def spawn_ranks(args):
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     log("bench.py: launching", " ".join(cmd))
     env = dict(os.environ)
     env["BENCH_N"] = str(args.n)   # (torch.distributed.run's parser trips over a script option called --n)
@@ -411,12 +439,6 @@ def device_state():
 
 
 TIMED_SOLVES = 3
-GS256_ITERS_REF = SOR256_ITERS_REF = None   # filled in from tests/golden/p7_sweeps_256.npz when that fixture is present
-try:
-    GS256_ITERS_REF = int(np.load(os.path.join(ROOT, "tests", "golden", "p7_sweeps_256.npz"))["gscf_iters"])
-    SOR256_ITERS_REF = int(np.load(os.path.join(ROOT, "tests", "golden", "p7_sweeps_256.npz"))["sor11_iters"])
-except Exception:
-    pass
 
 
 def other_configs_leg():
@@ -425,6 +447,12 @@ def other_configs_leg():
     never instead of it; iteration counts are the compiled reference's (tests/golden/configs_full.npz, p7_sweeps.npz pin
     them in the test suite)."""
     from faspsolver_amd import _types as T
+    GS256_ITERS_REF = SOR256_ITERS_REF = None   # filled in from tests/golden/p7_sweeps_256.npz when that fixture is present
+    try:
+        GS256_ITERS_REF = int(np.load(os.path.join(ROOT, "tests", "golden", "p7_sweeps_256.npz"))["gscf_iters"])
+        SOR256_ITERS_REF = int(np.load(os.path.join(ROOT, "tests", "golden", "p7_sweeps_256.npz"))["sor11_iters"])
+    except Exception:
+        pass
     res = {}
     try:   # config 3: P7(128) (x) B3, UA-AMG (VMB) + block Jacobi + VGMRES(30)
         ia, ja, a, f0, ue = fa.poisson7pt(128)
@@ -507,6 +535,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=int(os.environ.get("BENCH_N", "256")))
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: plain-CSR SpMV, ceilings, parity against the reference, "
+                         "CPU baselines, the variable-coefficient solve, the other configurations (multi-GPU: the CPU baseline, "
+                         "the diagnostic solve, the parity entry, the 512^3 leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (solution, residual history, iterations and relres) as .npy files into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variable", action="store_true", help="skip the variable-coefficient second solve")
     ap.add_argument("--no-extra", action="store_true", help="skip the other configurations (configs 3 and 5 at full size, GS defaults at 128^3 and 256^3)")
@@ -515,6 +549,8 @@ def main():
     ap.add_argument("--only-variable", action="store_true",
                     help="profiling runs: only the variable-coefficient solve (tools/profile.sh <tag> variable)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -576,6 +612,8 @@ def main():
     x = H.get_solution()
     log(f"solve: {st} iterations, relres {stats.relres:.10e}, {ms_per_step:.2f} ms/solve, "
         f"coarse its {stats.coarse_iters}, max|x-u_exact| {np.max(np.abs(x-ue)):.3e}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, hist, int(st), stats.relres)
 
     B = spmv_bytes(m, m, nnz)
     kind, matrix_bytes = H.kernel_info(0, 0)
@@ -584,7 +622,7 @@ def main():
     roof = roofline_entry(kind, moved, kernel_ms, int(stats.spmv_launches) * args.steps, workload="constant", n=n,
                           note=("the operator is stored losslessly coded (2 bytes per row + a 27-entry pattern table): "
                                 "bytes_per_launch is what this kernel has to move, not SURVEY 8(d)'s plain-CSR figure "
-                                f"({B} B); the plain-CSR kernel of the same operator is timed in the same run: "
+                                f"({B} B); the plain-CSR kernel of the same operator is timed in the same run with --full: "
                                 "roofline_plain_csr") if coded else None)
     roof["plain_csr_algorithmic_bytes"] = B
 
@@ -592,7 +630,7 @@ def main():
     # one warm-up and two timed solves: every coded operator of the hierarchy then runs its plain-CSR kernel; HIP events around the
     # level-0 t = A p launches).  SURVEY 8(d)'s bytes over that time = north_star's "SpMV >= 60 % of the HBM roofline".
     plain = None
-    if coded and not args.no_plain:
+    if coded and args.full and not args.no_plain:
         try:
             L.fasp_hip_tune(b"compress", 0)
             pkind, _pb = H.kernel_info(0, 0)
@@ -641,7 +679,7 @@ def main():
     ceilings = None
     try:
         out3 = (C.c_double * 3)()
-        if not args.no_ceilings and L.fasp_hip_measure_ceilings(out3, C.c_size_t(1 << 30), 5) == 0:
+        if args.full and not args.no_ceilings and L.fasp_hip_measure_ceilings(out3, C.c_size_t(1 << 30), 5) == 0:
             ceilings = {"unit": "GB/s", "read": out3[0], "copy": out3[1], "triad": out3[2],
                         "buffer_bytes": 1 << 30,
                         "note": "16 bytes per lane, 1024-block grid, HIP events; roofline fractions use the nominal 8000 GB/s",
@@ -668,27 +706,28 @@ def main():
     # The parity statement of the line: against the REFERENCE's own run of this solve (tests/golden/p7_scale.npz, written by
     # tools/gen_golden_f5*.py from the compiled reference; a committed fixture, not the oracle): iteration count, final
     # relative residual (absolute bar 1e-10; relative deviation printed beside it), the residual history.
-    try:
-        z = np.load(os.path.join(ROOT, "tests", "golden", "p7_scale.npz"))
-        if f"n{n}_iters" in z.files:
-            it_ref, rr_ref = int(z[f"n{n}_iters"]), float(z[f"n{n}_relres"])
-            pr = {"iters_gpu": int(st), "iters_reference": it_ref, "relres_gpu": stats.relres, "relres_reference": rr_ref,
-                  "abs_dev_relres": abs(stats.relres - rr_ref), "rel_dev_relres": abs(stats.relres - rr_ref) / rr_ref,
-                  "source": "compiled reference (tests/golden/p7_scale.npz)"}
-            ok = int(st) == it_ref and abs(stats.relres - rr_ref) <= 1e-10 and abs(stats.relres - rr_ref) <= 1e-6 * rr_ref
-            if f"n{n}_hist" in z.files:
-                hr = z[f"n{n}_hist"]
-                hd = np.concatenate([hist[:-2], hist[-1:]])   # (the device history ends with recurrence and true residual of the last iteration)
-                if len(hd) == len(hr):
-                    pr["max_rel_dev_residual_history"] = float(np.max(np.abs(hd[:-1] - hr[:-1]) / hr[:-1]))
-                    ok = ok and pr["max_rel_dev_residual_history"] <= 1e-8
-                else:
-                    ok = False
-            pr["ok"] = bool(ok)
-            out["parity_reference"] = pr
-    except Exception as e:
-        log(f"parity_reference unavailable: {e!r}")
-    if not args.no_cpu_baseline:
+    if args.full:
+        try:
+            z = np.load(os.path.join(ROOT, "tests", "golden", "p7_scale.npz"))
+            if f"n{n}_iters" in z.files:
+                it_ref, rr_ref = int(z[f"n{n}_iters"]), float(z[f"n{n}_relres"])
+                pr = {"iters_gpu": int(st), "iters_reference": it_ref, "relres_gpu": stats.relres, "relres_reference": rr_ref,
+                      "abs_dev_relres": abs(stats.relres - rr_ref), "rel_dev_relres": abs(stats.relres - rr_ref) / rr_ref,
+                      "source": "compiled reference (tests/golden/p7_scale.npz)"}
+                ok = int(st) == it_ref and abs(stats.relres - rr_ref) <= 1e-10 and abs(stats.relres - rr_ref) <= 1e-6 * rr_ref
+                if f"n{n}_hist" in z.files:
+                    hr = z[f"n{n}_hist"]
+                    hd = np.concatenate([hist[:-2], hist[-1:]])   # (the device history ends with recurrence and true residual of the last iteration)
+                    if len(hd) == len(hr):
+                        pr["max_rel_dev_residual_history"] = float(np.max(np.abs(hd[:-1] - hr[:-1]) / hr[:-1]))
+                        ok = ok and pr["max_rel_dev_residual_history"] <= 1e-8
+                    else:
+                        ok = False
+                pr["ok"] = bool(ok)
+                out["parity_reference"] = pr
+        except Exception as e:
+            log(f"parity_reference unavailable: {e!r}")
+    if args.full and not args.no_cpu_baseline:
         try:
             cb, its_cpu, rr_cpu, hist_dev = cpu_baseline(H, ia, ja, a, f, int(st), hist,
                                                          float(os.environ.get("BENCH_CPU_BUDGET_S", "15")), baseline_candidates())
@@ -704,14 +743,14 @@ def main():
             out.setdefault("cpu_baseline", None)
     H.close()
 
-    if not args.no_variable:
+    if args.full and not args.no_variable:
         out["variable_coefficient"] = variable_leg(n, (ia, ja, a, f, ue), itp, amgp, timed_solves)
         if out["variable_coefficient"]:   # the general-matrix number inside the keys the driver keeps
             vc = out["variable_coefficient"]
             out["roofline"]["variable_coefficient"] = {"ms_per_step": vc["ms_per_step"], "iterations": vc["iterations"],
                                                        "level0_spmv_frac": vc["roofline"]["frac"], "level0_kernel": vc["roofline"]["kernel"]}
             out["config"]["variable_coefficient_ms_per_step"] = vc["ms_per_step"]
-    if not args.no_extra and args.gpus == 1:
+    if args.full and not args.no_extra and args.gpus == 1:
         del ia, ja, a
         out["other_configs"] = other_configs_leg()
     print(json.dumps(out), flush=True)

@@ -95,9 +95,10 @@ def main(args, rank, world, local_rank):
             st = L.fasp_hip_comm_init_ipc(rank, world, name.encode())
     assert st == 0, f"comm init -> {st}"
 
-    def measure(n, steps, warmup, with_cpu):
-        """One size: host setup on rank 0, partition + upload, warm-up and timed solves, the diagnostic solve; rank 0 returns the line's
-        dictionary, the other ranks None.  Every rank takes the same path (collectives inside)."""
+    def measure(n, steps, warmup, with_cpu, full, dump=None):
+        """One size: host setup on rank 0, partition + upload, warm-up and timed solves, with `full` the diagnostic solve; rank 0
+        returns the line's dictionary (and writes the outputs of the last timed step into `dump`), the other ranks None.  Every rank
+        takes the same path (collectives inside)."""
         out = None
         # ONE host setup per node (SURVEY.md section 8e): rank 0 generates the system, runs the AMG setup and publishes
         # the host hierarchy in a shared-memory segment; the other ranks map it and upload the rows they own.
@@ -155,30 +156,34 @@ def main(args, rank, world, local_rank):
         assert torch.equal(lo, hi), "ranks disagree on iteration count / residual"
         L.fasp_hip_comm_stats(cst, 1)
         per_solve = [v / steps for v in cst]
-        # ONE more solve in the communicator's diagnostic mode: the stream is drained around every exchange / all-reduce /
-        # all-gather, so each call's time is its own and what is left of the solve is this rank's kernels.  A breakdown of a
-        # serialised solve (no overlap of the halo with the interior rows), never part of `value`.
-        L.fasp_hip_comm_timing(1)
-        dist.barrier()
-        td = time.perf_counter()
-        st_d, hist_d, stats_d = H.solve_resident(itp)
-        L.fasp_hip_device_synchronize()
-        t_diag = time.perf_counter() - td
-        L.fasp_hip_comm_timing(0)
-        L.fasp_hip_comm_stats(cst, 1)
-        diag = torch.tensor([t_diag, cst[5], cst[6], cst[7], stats_d.solve_seconds], dtype=torch.float64)
-        dmax = diag.clone(); dmin = diag.clone()
-        dist.all_reduce(dmax, op=dist.ReduceOp.MAX); dist.all_reduce(dmin, op=dist.ReduceOp.MIN)
+        # the solution of the last timed solve, assembled from the ranks' disjoint row ranges (read before any other solve)
+        x = H.get_solution()  # own rows filled, the rest zero
+        xt = torch.from_numpy(x)
+        dist.all_reduce(xt)   # disjoint row ranges: sum assembles the global solution
+        err = float(np.max(np.abs(xt.numpy() - ue)))
+        if rank == 0 and dump:
+            B.dump_outputs(dump, xt.numpy(), hist, int(st), stats.relres)
+        if full:
+            # ONE more solve in the communicator's diagnostic mode: the stream is drained around every exchange / all-reduce /
+            # all-gather, so each call's time is its own and what is left of the solve is this rank's kernels.  A breakdown of a
+            # serialised solve (no overlap of the halo with the interior rows), never part of `value`.
+            L.fasp_hip_comm_timing(1)
+            dist.barrier()
+            td = time.perf_counter()
+            st_d, hist_d, stats_d = H.solve_resident(itp)
+            L.fasp_hip_device_synchronize()
+            t_diag = time.perf_counter() - td
+            L.fasp_hip_comm_timing(0)
+            L.fasp_hip_comm_stats(cst, 1)
+            diag = torch.tensor([t_diag, cst[5], cst[6], cst[7], stats_d.solve_seconds], dtype=torch.float64)
+            dmax = diag.clone(); dmin = diag.clone()
+            dist.all_reduce(dmax, op=dist.ReduceOp.MAX); dist.all_reduce(dmin, op=dist.ReduceOp.MIN)
         levels_info = [H.dist_info(l) for l in range(H.num_levels)]
         # where every rank sits: PCI bus ids, gathered over gloo (an 8-GPU run is only a measurement when they are all different)
         idbuf2 = C.create_string_buffer(64)
         L.fasp_hip_device_identity(idbuf2, 64)
         ids = [None] * world
         dist.all_gather_object(ids, idbuf2.value.decode())
-        x = H.get_solution()  # own rows filled, the rest zero
-        xt = torch.from_numpy(x)
-        dist.all_reduce(xt)   # disjoint row ranges: sum assembles the global solution
-        err = float(np.max(np.abs(xt.numpy() - ue)))
 
         if rank == 0:
             ms_per_step = 1e3 * elapsed / steps
@@ -209,18 +214,20 @@ def main(args, rank, world, local_rank):
                          "per_solve": {"halo_exchanges": per_solve[0], "allreduces": per_solve[1], "allgathers": per_solve[2],
                                        "halo_MB_sent_rank0": per_solve[3] * 8e-6, "allgather_MB_rank0": per_solve[4] * 8e-6,
                                        "allreduces_per_iteration": per_solve[1] / max(1, int(st))},
-                         "diagnostic_solve_ms": {"note": "one solve with the stream drained around every communicator call (serialised: no halo / interior overlap)",
-                                                 "total_max": float(dmax[4]) * 1e3, "halo_exchange_max": float(dmax[1]) * 1e3, "halo_exchange_min": float(dmin[1]) * 1e3,
-                                                 "allreduce_max": float(dmax[2]) * 1e3, "allreduce_min": float(dmin[2]) * 1e3,
-                                                 "allgather_max": float(dmax[3]) * 1e3, "allgather_min": float(dmin[3]) * 1e3,
-                                                 "kernels_and_host_rank_max": float(dmax[4] - dmin[1] - dmin[2] - dmin[3]) * 1e3},
                          "coarse_cg_iterations": int(stats.coarse_iters), "vcycles": int(stats.vcycles),
                          "levels": [{"level": l, "distributed": int(not i["replicated"]), "rows": i["nglobal"], "rank0_rows": i["nloc"],
                                      "rank0_ghosts": i["nghost"], "rank0_sends": i["nsend"]} for l, i in enumerate(levels_info)]},
             }
+            if full:
+                out["comm"]["diagnostic_solve_ms"] = {
+                    "note": "one solve with the stream drained around every communicator call (serialised: no halo / interior overlap)",
+                    "total_max": float(dmax[4]) * 1e3, "halo_exchange_max": float(dmax[1]) * 1e3, "halo_exchange_min": float(dmin[1]) * 1e3,
+                    "allreduce_max": float(dmax[2]) * 1e3, "allreduce_min": float(dmin[2]) * 1e3,
+                    "allgather_max": float(dmax[3]) * 1e3, "allgather_min": float(dmin[3]) * 1e3,
+                    "kernels_and_host_rank_max": float(dmax[4] - dmin[1] - dmin[2] - dmin[3]) * 1e3}
             # the reference's own figures for this solve where they are pinned (tests/golden/configs_full.npz): what a first run on N GPUs is read against
             pins = {256: (14, 6.3426837114e-09), 512: (31, 6.70717e-09)}
-            if n in pins:
+            if full and n in pins:
                 out["parity_reference"] = {"iters_gpu": int(st), "iters_reference": pins[n][0], "relres_gpu": stats.relres, "relres_reference": pins[n][1],
                                            "ok": bool(int(st) == pins[n][0] and abs(stats.relres - pins[n][1]) <= 1e-10)}
             if with_cpu:
@@ -238,13 +245,14 @@ def main(args, rank, world, local_rank):
         H.close()
         return out
 
-    out = measure(args.n, args.steps, args.warmup, not args.no_cpu_baseline)
+    out = measure(args.n, args.steps, args.warmup, args.full and not args.no_cpu_baseline, args.full, args.dump_outputs)
     # north_star quotes its scaling target (>= 3.5 x at 8 GPUs) at 512^3; the metric's own size, 256^3, is latency- and Amdahl-bound on
-    # eight GPUs.  An 8-GPU run of the default size therefore carries the 512^3 solve too, INSIDE the one JSON
-    # line (key "at_512"; BENCH_SCALE_512=0 skips it, =1 forces it for any N).  Decided from the environment alone: every rank agrees.
-    want512 = os.environ.get("BENCH_SCALE_512", "1" if (world == 8 and args.n == 256) else "0") == "1" and args.n != 512
+    # eight GPUs.  An 8-GPU --full run of the default size therefore carries the 512^3 solve too, INSIDE the one
+    # JSON line (key "at_512"; BENCH_SCALE_512=0 skips it, =1 forces it for any N).  Decided from the arguments and the environment
+    # alone: every rank agrees.
+    want512 = os.environ.get("BENCH_SCALE_512", "1" if (world == 8 and args.n == 256 and args.full) else "0") == "1" and args.n != 512
     if want512:
-        o2 = measure(512, max(1, min(args.steps, 3)), 1, False)
+        o2 = measure(512, max(1, min(args.steps, 3)), 1, False, True)
         if rank == 0 and o2 is not None:
             out["at_512"] = {k: o2[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "iterations", "relres", "setup_seconds",
                                                 "host_setup_seconds", "parity_reference", "roofline") if k in o2}

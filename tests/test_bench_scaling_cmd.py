@@ -5,7 +5,8 @@ problem, solve, and rank 0 prints ONE JSON line.  On a box with one GPU the rank
 line by the transport's name); on the 8-GPU node the same command is the measurement.  SURVEY.md section 8(e).
 
 These tests are the first place the driver's environment executes that path: rc 0, one JSON line, n_gpus as asked, the
-transport named, the single-GPU iteration count, the reference's own figures where they are pinned.
+transport named, the single-GPU iteration count, the reference's own figures where they are pinned (`--full`: the parity entry
+and the diagnostic solve are not part of a plain run).
 """
 import json
 import os
@@ -24,7 +25,7 @@ def _run_bench(n, gpus, comm, steps=2, warmup=1, timeout=900):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup),
-                        "--no-cpu-baseline"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
+                        "--full", "--no-cpu-baseline"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p, lines
 
@@ -32,7 +33,7 @@ def _run_bench(n, gpus, comm, steps=2, warmup=1, timeout=900):
 @pytest.mark.gpu
 @pytest.mark.parametrize("comm", ["auto", "rccl"])
 def test_bench_scaling_command_two_ranks(comm):
-    """BENCH_N=64 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline.  comm = auto: the transport is whatever the probes
+    """BENCH_N=64 python bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu-baseline.  comm = auto: the transport is whatever the probes
     find working on every rank; comm = rccl on a box whose ranks share one GPU: the communicator cannot be created there and the
     run falls back to the peer-window transport TOGETHER (every rank, cleanly) instead of hanging or failing."""
     p, lines = _run_bench(64, 2, comm)
