@@ -50,6 +50,10 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_blas_dcsr_vmv", "fasp_blas_dcsr_mxv_agg", "fasp_blas_dcsr_aAxpy_agg", "fasp_blas_darray_ax",
     "fasp_blas_darray_axpyz", "fasp_blas_darray_norm1", "fasp_darray_cp", "fasp_darray_set", "fasp_dvec_isnan",
     "fasp_hip_time_matrix", "fasp_hip_bsr_dist_info", "fasp_hip_seq_schedule_selftest", "fasp_hip_seq_chain_selftest", "fasp_hip_cluster_order", "fasp_hip_permute_csr", "fasp_hip_comm_init_ipc", "fasp_hip_comm_stats", "fasp_hip_comm_timing", "fasp_hip_estream_selftest",
+    "fasp_param_ilu_init", "fasp_ilu_data_create", "fasp_ilu_data_free", "fasp_mem_iludata_check", "fasp_ilu_dcsr_setup",
+    "fasp_precond_ilu", "fasp_precond_ilu_forward", "fasp_precond_ilu_backward", "fasp_solver_dcsr_krylov_ilu",
+    "fasp_solver_dcsr_krylov_ilu_M", "fasp_smoother_dcsr_ilu", "fasp_fwrapper_dcsr_krylov_ilu_",
+    "fasp_hip_ilu_resident_count", "fasp_hip_ilu_time",
 ]
 
 
@@ -199,6 +203,30 @@ def lib():
     L.fasp_hip_dist_get_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, P(T.dCSRmat)]
     L.fasp_hip_dist_get_list.argtypes = [C.c_void_p, C.c_int, C.c_int, P(T.ivector)]
     _lib = L
+    # ILU preconditioner (csrc/ilu_setup.cpp, csrc/ilu.hip.h)
+    L.fasp_param_ilu_init.argtypes = [P(T.ILU_param)]
+    L.fasp_param_ilu_init.restype = None
+    L.fasp_ilu_data_create.argtypes = [C.c_int, C.c_int, P(T.ILU_data)]
+    L.fasp_ilu_data_create.restype = None
+    L.fasp_ilu_data_free.argtypes = [P(T.ILU_data)]
+    L.fasp_ilu_data_free.restype = None
+    L.fasp_mem_iludata_check.argtypes = [P(T.ILU_data)]
+    L.fasp_mem_iludata_check.restype = C.c_short
+    L.fasp_ilu_dcsr_setup.argtypes = [P(T.dCSRmat), P(T.ILU_data), P(T.ILU_param)]
+    L.fasp_ilu_dcsr_setup.restype = C.c_short
+    for f in ("fasp_precond_ilu", "fasp_precond_ilu_forward", "fasp_precond_ilu_backward"):
+        getattr(L, f).argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+        getattr(L, f).restype = None
+    L.fasp_solver_dcsr_krylov_ilu.argtypes = [P(T.dCSRmat), P(T.dvector), P(T.dvector), P(T.ITS_param), P(T.ILU_param)]
+    L.fasp_solver_dcsr_krylov_ilu_M.argtypes = [P(T.dCSRmat), P(T.dvector), P(T.dvector), P(T.ITS_param),
+                                                P(T.ILU_param), P(T.dCSRmat)]
+    L.fasp_smoother_dcsr_ilu.argtypes = [P(T.dCSRmat), P(T.dvector), P(T.dvector), C.c_void_p]
+    L.fasp_smoother_dcsr_ilu.restype = None
+    L.fasp_fwrapper_dcsr_krylov_ilu_.argtypes = [P(C.c_int), P(C.c_int), T.c_int_p, T.c_int_p, T.c_double_p,
+                                                 T.c_double_p, T.c_double_p, P(C.c_double), P(C.c_int), P(C.c_int)]
+    L.fasp_fwrapper_dcsr_krylov_ilu_.restype = None
+    L.fasp_hip_ilu_time.argtypes = [P(T.ILU_data), C.c_int, C.c_int, T.c_double_p]
+    L.fasp_hip_ilu_time.restype = C.c_double
     return L
 
 

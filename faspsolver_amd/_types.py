@@ -24,6 +24,7 @@ ERROR_SOLVER_PRECTYPE = -41
 ERROR_SOLVER_STAG = -42
 ERROR_SOLVER_SOLSTAG = -43
 ERROR_SOLVER_TOLSMALL = -44
+ERROR_SOLVER_ILUSETUP = -45
 ERROR_SOLVER_MAXIT = -48
 ERROR_UNKNOWN = -99
 
@@ -34,6 +35,8 @@ SOLVER_GMRES = 4
 SOLVER_MinRes, SOLVER_GCG, SOLVER_GCR = 3, 7, 8
 STOP_REL_RES, STOP_REL_PRECRES, STOP_MOD_REL_RES = 1, 2, 3
 PREC_NULL, PREC_DIAG, PREC_AMG, PREC_FMG = 0, 1, 2, 3
+PREC_ILU, PREC_SCHWARZ = 4, 5
+ILUk, ILUt, ILUtp = 1, 2, 3
 CLASSIC_AMG, SA_AMG, UA_AMG = 1, 2, 3
 V_CYCLE, W_CYCLE, AMLI_CYCLE, NL_AMLI_CYCLE, VW_CYCLE, WV_CYCLE = 1, 2, 3, 4, 12, 21
 SMOOTHER_JACOBI, SMOOTHER_GS, SMOOTHER_SGS, SMOOTHER_CG, SMOOTHER_SOR = 1, 2, 3, 4, 5
@@ -155,3 +158,18 @@ PRECOND_FCT = C.CFUNCTYPE(None, c_double_p, c_double_p, C.c_void_p)
 class precond(C.Structure):
     """fasp.h:1095-1103: preconditioner data + action z = B r."""
     _fields_ = [("data", C.c_void_p), ("fct", PRECOND_FCT)]
+
+
+class ILU_param(C.Structure):
+    """fasp.h:404"""
+    _fields_ = [("print_level", C.c_short), ("ILU_type", C.c_short), ("ILU_lfil", C.c_int),
+                ("ILU_droptol", C.c_double), ("ILU_relax", C.c_double), ("ILU_permtol", C.c_double)]
+
+
+class ILU_data(C.Structure):
+    """fasp.h:651: MSR factor (ijlu / luval, nzlu entries), work space, ILUtp permutation (1-based)."""
+    _fields_ = [("A", C.POINTER(dCSRmat)), ("type", C.c_int), ("row", C.c_int), ("col", C.c_int),
+                ("nzlu", C.c_int), ("ijlu", c_int_p), ("luval", c_double_p), ("nb", C.c_int),
+                ("nwork", C.c_int), ("work", c_double_p), ("iperm", c_int_p), ("ncolors", C.c_int),
+                ("ic", c_int_p), ("icmap", c_int_p), ("uptr", c_int_p), ("nlevL", C.c_int), ("nlevU", C.c_int),
+                ("ilevL", c_int_p), ("ilevU", c_int_p), ("jlevL", c_int_p), ("jlevU", c_int_p)]

@@ -1,0 +1,547 @@
+// ilu.hip.h -- application of an incomplete LU factor on the device (PreCSR.c:198 / :263 / :317, ItrSmootherCSR.c:1280),
+// the residency of factors built by fasp_ilu_dcsr_setup (csrc/ilu_setup.cpp), fasp_ilu_data_free (PreDataInit.c:445) and the
+// solver entry points around them (SolCSR.c:588 / :668).  Part of the single translation unit solver.hip (included inside its
+// extern "C" block; the kernels and the C++ helpers sit in an extern "C++" block).
+//
+// The factor (MSR: ijlu / luval, see ilu_setup.cpp) is two triangular operators:
+//   L: row i's entries in storage order up to the first one with column >= i; y_i = r_i - l_i1 y_c1 - l_i2 y_c2 - ...
+//   U: row i's entries from the END of the row back to the first one with column <= i; z_i = (y_i - u_i1 z_c1 - ...) * luval[i]
+// exactly the reference's loops: one product subtracted at a time in that order, the stored inverse pivot as a multiplier, no
+// fused multiply-add (the build has -ffp-contract=off and nothing here asks for one), so z is bit for bit the reference's.
+//
+// Schedule (host, at upload): level(i) = 1 + the largest level of the rows i reads (0: reads none).  The rows of a level are
+// independent; each level is cut into chunks of 64 rows (one wavefront, one row per lane, the sum chain of a row in its own
+// lane), the last chunk of a level padded.  A chunk's entries are an ELL slab: entry k of its 64 rows at [base + 64 k, +64), so
+// the lanes of a wavefront read consecutive addresses while every row is still summed in its own order.  Two forms:
+//   level launches   one launch per level (k_ilu_level); the kernel boundary hands the level on.  The fallback, and the form
+//                    the tests compare against.
+//   single launch    (k_ilu_flow) every wavefront draws chunks in level order from a ticket counter; the output vector is
+//                    filled with a sentinel (all bits set) first and each value is published by one 8-byte agent-scope store
+//                    (the data is the flag: cdna_hip_programming.md Guideline 16, R2), read by agent-scope loads that spin
+//                    while they see the sentinel.  A chunk only waits for rows of lower levels, which hold lower tickets,
+//                    drawn by wavefronts that are running: no residency assumption.  Spins are bounded (flow_give_up: 2 s,
+//                    then the error word, the solve fails loudly and later solves use level launches).
+// The form follows the schedule's depth (single launch beyond ILU_FLOW_MIN_LEVELS levels); fasp_hip_tune("ilu_form", 0 / 1)
+// forces one.  ILU(0) of P7(n) has 3 n - 2 levels per triangle: 766 at 256^3.
+
+#ifndef ILU_FLOW_MIN_LEVELS
+#define ILU_FLOW_MIN_LEVELS 24
+#endif
+
+extern "C++" {
+
+struct IluArgs {
+    const int*       rows;    // [nchunk * 64] row of each slot, -1: padding
+    const int*       len;     // [nchunk * 64] entries of the slot's row
+    const long long* cbase;   // [nchunk] first slab entry of the chunk
+    const int*       cols;    // slab: column of entry k of slot s at cbase[c] + 64 k + lane
+    const double*    vals;
+    const double*    diag;    // U: luval[row] per slot; L: nullptr
+    const double*    in;      // right-hand side (indexed by row)
+    double*          out;     // solution (indexed by row)
+    unsigned*        sync;    // single launch: [0] ticket, [1] error word, [6..7] host-mapped error word (flow_give_up)
+    int              nchunk;
+};
+
+template <bool HAS_D, bool SPIN>
+__device__ __forceinline__ void ilu_chunk(const IluArgs& a, int c, int lane)
+{
+    typedef __attribute__((address_space(1))) unsigned long long gu64;
+    const int s = c * 64 + lane;
+    const int row = a.rows[s];
+    if (row < 0) return;
+    const int len = a.len[s];
+    const long long e0 = a.cbase[c] + lane;
+    double acc = a.in[row];
+    unsigned spins = 0;
+    unsigned long long t0 = 0;
+    for (int k = 0; k < len; ++k) {
+        const int col = a.cols[e0 + 64ll * k];
+        const double v = a.vals[e0 + 64ll * k];
+        double x;
+        if (SPIN) {
+            unsigned long long bits = __hip_atomic_load((gu64*)(a.out + col), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            while (bits == ~0ull) {
+                if (flow_give_up(a.sync, spins, t0)) break;
+                __builtin_amdgcn_s_sleep(1);
+                bits = __hip_atomic_load((gu64*)(a.out + col), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            x = __longlong_as_double((long long)bits);
+        } else {
+            x = a.out[col];
+        }
+        acc = acc - v * x;
+    }
+    if (HAS_D) acc = acc * a.diag[s];
+    if (SPIN) __hip_atomic_store((gu64*)(a.out + row), (unsigned long long)__double_as_longlong(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else a.out[row] = acc;
+}
+
+// one level: chunks [c0, c1), four wavefronts per workgroup, one chunk each
+template <bool HAS_D>
+__global__ __launch_bounds__(256) void k_ilu_level(IluArgs a, int c0, int c1)
+{
+    const int c = c0 + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (c < c1) ilu_chunk<HAS_D, false>(a, c, (int)(threadIdx.x & 63));
+}
+
+// all levels in one launch: wavefronts draw chunks in level order
+template <bool HAS_D>
+__global__ __launch_bounds__(256) void k_ilu_flow(IluArgs a)
+{
+    typedef __attribute__((address_space(1))) unsigned gu32;
+    const int lane = (int)(threadIdx.x & 63);
+    for (;;) {
+        int c = 0;
+        if (lane == 0) c = (int)__hip_atomic_fetch_add((gu32*)a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        c = __shfl(c, 0);
+        if (c >= a.nchunk) break;
+        ilu_chunk<HAS_D, true>(a, c, lane);
+    }
+}
+
+namespace {
+
+// one triangle on the device
+struct IluTri {
+    int nlev = 0, nchunk = 0, maxlen = 0;
+    long long nent = 0, nreal = 0;   // slab entries (padded) / actual entries
+    std::vector<int> lvl_chunk;      // host: first chunk of each level, nlev + 1
+    int *rows = nullptr, *len = nullptr, *cols = nullptr;
+    long long* cbase = nullptr;
+    double *vals = nullptr, *diag = nullptr;
+};
+struct IluDev {
+    int      n = 0;
+    IluTri   L, U;
+    double  *y = nullptr, *r = nullptr, *z = nullptr;
+    unsigned* sync = nullptr;
+    std::vector<void*> owned;
+};
+
+void ilu_dev_destroy(IluDev* D)
+{
+    if (!D) return;
+    for (void* p : D->owned) (void)hipFree(p);
+    delete D;
+}
+
+template <class T>
+bool ilu_put(IluDev* D, T** dst, const std::vector<T>& src, size_t count)
+{
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) return false;
+    D->owned.push_back(p);
+    *dst = static_cast<T*>(p);
+    if (!src.empty()) return hipMemcpy(p, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice) == hipSuccess;
+    return true;
+}
+
+// the entries of row i that one triangle reads, in the order they are subtracted
+void ilu_row_entries(const ILU_data* d, int i, bool upper, std::vector<int>& pos)
+{
+    pos.clear();
+    const int n = d->row;
+    const int b = d->ijlu[i], e = d->ijlu[i + 1];
+    if (!upper) {
+        if (i == 0) return;   // the reference starts the forward sweep at row 1
+        for (int p = b; p < e && d->ijlu[p] < i; ++p) pos.push_back(p);
+    } else {
+        if (i == n - 1) return;   // ... and the backward sweep at row n - 2
+        for (int p = e - 1; p >= b && d->ijlu[p] > i; --p) pos.push_back(p);
+    }
+}
+
+int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
+{
+    const int n = d->row;
+    std::vector<int> level((size_t)n, 0), pos;
+    int nlev = 0;
+    for (int t = 0; t < n; ++t) {
+        const int i = upper ? n - 1 - t : t;
+        ilu_row_entries(d, i, upper, pos);
+        int lv = 0;
+        for (int p : pos) {
+            const int c = d->ijlu[p];
+            if (c < 0 || c >= n) return ERROR_DATA_STRUCTURE;
+            lv = std::max(lv, level[(size_t)c] + 1);
+        }
+        level[(size_t)i] = lv;
+        nlev = std::max(nlev, lv + 1);
+    }
+    // rows by level (ascending row index inside a level), cut into chunks of 64
+    std::vector<int> cnt((size_t)nlev + 1, 0);
+    for (int i = 0; i < n; ++i) ++cnt[(size_t)level[(size_t)i] + 1];
+    std::vector<int> first((size_t)nlev + 1, 0);
+    for (int l = 0; l < nlev; ++l) first[(size_t)l + 1] = first[(size_t)l] + cnt[(size_t)l + 1];
+    std::vector<int> order((size_t)n);
+    {
+        std::vector<int> at(first.begin(), first.end() - 1);
+        for (int i = 0; i < n; ++i) order[(size_t)at[(size_t)level[(size_t)i]]++] = i;
+    }
+    T.nlev = nlev;
+    T.lvl_chunk.assign((size_t)nlev + 1, 0);
+    for (int l = 0; l < nlev; ++l) T.lvl_chunk[(size_t)l + 1] = T.lvl_chunk[(size_t)l] + (cnt[(size_t)l + 1] + 63) / 64;
+    T.nchunk = T.lvl_chunk[(size_t)nlev];
+    const size_t nslot = (size_t)T.nchunk * 64;
+    std::vector<int> rows(nslot, -1), len(nslot, 0);
+    std::vector<long long> cbase((size_t)T.nchunk, 0);
+    std::vector<double> diag(upper ? nslot : 0, 0.0);
+    long long nent = 0;
+    T.maxlen = 0; T.nreal = 0;
+    for (int l = 0; l < nlev; ++l)
+        for (int c = T.lvl_chunk[(size_t)l]; c < T.lvl_chunk[(size_t)l + 1]; ++c) {
+            int kmax = 0;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int q = first[(size_t)l] + (c - T.lvl_chunk[(size_t)l]) * 64 + lane;
+                if (q >= first[(size_t)l + 1]) break;
+                const int i = order[(size_t)q];
+                ilu_row_entries(d, i, upper, pos);
+                rows[(size_t)c * 64 + lane] = i;
+                len[(size_t)c * 64 + lane] = (int)pos.size();
+                if (upper) diag[(size_t)c * 64 + lane] = d->luval[i];
+                kmax = std::max(kmax, (int)pos.size());
+                T.nreal += (long long)pos.size();
+            }
+            cbase[(size_t)c] = nent;
+            nent += 64ll * kmax;
+            T.maxlen = std::max(T.maxlen, kmax);
+        }
+    T.nent = nent;
+    std::vector<int> cols((size_t)nent, 0);
+    std::vector<double> vals((size_t)nent, 0.0);
+    for (int c = 0; c < T.nchunk; ++c)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int i = rows[(size_t)c * 64 + lane];
+            if (i < 0) continue;
+            ilu_row_entries(d, i, upper, pos);
+            for (size_t k = 0; k < pos.size(); ++k) {
+                const size_t e = (size_t)cbase[(size_t)c] + 64 * k + (size_t)lane;
+                cols[e] = d->ijlu[pos[k]];
+                vals[e] = d->luval[pos[k]];
+            }
+        }
+    if (!ilu_put(D, &T.rows, rows, nslot) || !ilu_put(D, &T.len, len, nslot) || !ilu_put(D, &T.cbase, cbase, cbase.size()) ||
+        !ilu_put(D, &T.cols, cols, cols.size()) || !ilu_put(D, &T.vals, vals, vals.size()))
+        return ERROR_ALLOC_MEM;
+    if (upper && !ilu_put(D, &T.diag, diag, diag.size())) return ERROR_ALLOC_MEM;
+    return FASP_SUCCESS;
+}
+
+// the device copy of a factor (nullptr: no device, or an inconsistent factor -- *st says which)
+IluDev* ilu_upload(const ILU_data* d, int* st)
+{
+    *st = FASP_SUCCESS;
+    if (ctx_init() < 0) { *st = ERROR_MISC; return nullptr; }
+    if (!d || d->row <= 0 || !d->ijlu || !d->luval) { *st = ERROR_INPUT_PAR; return nullptr; }
+    IluDev* D = new IluDev;
+    D->n = d->row;
+    const std::vector<double> none;
+    const std::vector<unsigned> sync0(16, 0u);
+    int e = ilu_build_tri(D, d, false, D->L);
+    if (e == FASP_SUCCESS) e = ilu_build_tri(D, d, true, D->U);
+    if (e == FASP_SUCCESS && (!ilu_put(D, &D->y, none, (size_t)D->n) || !ilu_put(D, &D->r, none, (size_t)D->n) ||
+                              !ilu_put(D, &D->z, none, (size_t)D->n) || !ilu_put(D, &D->sync, sync0, sync0.size())))
+        e = ERROR_ALLOC_MEM;
+    if (e == FASP_SUCCESS) {
+        const unsigned long long herr_addr = (unsigned long long)seq_err_device_word();
+        if (hipMemcpy(D->sync + 6, &herr_addr, 8, hipMemcpyHostToDevice) != hipSuccess) e = ERROR_MISC;
+    }
+    if (e != FASP_SUCCESS) { ilu_dev_destroy(D); *st = e; return nullptr; }
+    return D;
+}
+
+bool ilu_single_launch(const IluTri& T)
+{
+    if (g_tune.ilu_form == 0 || g_flow_disabled) return false;
+    if (g_tune.ilu_form == 1) return true;
+    return T.nlev > ILU_FLOW_MIN_LEVELS;
+}
+
+// out = T^-1 in (in, out: device vectors of n, not the same)
+int ilu_tri_solve(IluDev* D, const IluTri& T, bool upper, const double* in, double* out)
+{
+    IluArgs a{};
+    a.rows = T.rows; a.len = T.len; a.cbase = T.cbase; a.cols = T.cols; a.vals = T.vals; a.diag = T.diag;
+    a.in = in; a.out = out; a.sync = D->sync; a.nchunk = T.nchunk;
+    if (T.nchunk == 0) return FASP_SUCCESS;
+    if (ilu_single_launch(T)) {
+        HIPCK(hipMemsetAsync(out, 0xFF, sizeof(double) * (size_t)D->n, g_ctx.stream));   // the sentinel: not yet computed
+        HIPCK(hipMemsetAsync(D->sync, 0, 8, g_ctx.stream));                               // ticket counter + error word
+        const int grid = std::max(1, std::min((T.nchunk + 3) / 4, 1024));
+        if (upper) hipLaunchKernelGGL(k_ilu_flow<true>, dim3(grid), dim3(256), 0, g_ctx.stream, a);
+        else hipLaunchKernelGGL(k_ilu_flow<false>, dim3(grid), dim3(256), 0, g_ctx.stream, a);
+    } else {
+        for (int l = 0; l < T.nlev; ++l) {
+            const int c0 = T.lvl_chunk[(size_t)l], c1 = T.lvl_chunk[(size_t)l + 1];
+            const dim3 grid((unsigned)((c1 - c0 + 3) / 4));
+            if (upper) hipLaunchKernelGGL(k_ilu_level<true>, grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+            else hipLaunchKernelGGL(k_ilu_level<false>, grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+        }
+    }
+    return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
+}
+
+// which: 0 both triangles (fasp_precond_ilu), 1 L only (_forward), 2 U only (_backward).  out: a device vector other than in
+// (both triangles go through D->y).
+int ilu_apply(IluDev* D, int which, const double* in, double* out)
+{
+    if (seq_err_pending()) return seq_err_check();
+    if (which == 1) return ilu_tri_solve(D, D->L, false, in, out);
+    if (which == 2) return ilu_tri_solve(D, D->U, true, in, out);
+    const int st = ilu_tri_solve(D, D->L, false, in, D->y);
+    return st < 0 ? st : ilu_tri_solve(D, D->U, true, D->y, out);
+}
+
+// factors made by fasp_ilu_dcsr_setup: device copy made at the first application, dropped by fasp_ilu_data_free
+struct IluEntry { ILU_data* d; IluDev* dev; };
+std::vector<IluEntry> g_ilu_registry;
+
+IluEntry* ilu_entry(const ILU_data* d)
+{
+    for (IluEntry& e : g_ilu_registry)
+        if (e.d == d) return &e;
+    return nullptr;
+}
+
+// the device copy to apply `d` with: resident (registered factor) or made for this use (*tmp owns it)
+IluDev* ilu_device_of(ILU_data* d, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* st)
+{
+    *st = FASP_SUCCESS;
+    IluEntry* e = ilu_entry(d);
+    if (e) {
+        if (!e->dev) e->dev = ilu_upload(d, st);
+        return e->dev;
+    }
+    tmp.reset(ilu_upload(d, st));
+    return tmp.get();
+}
+
+int ilu_which(void (*fct)(double*, double*, void*))
+{
+    if (fct == fasp_precond_ilu) return 0;
+    if (fct == fasp_precond_ilu_forward) return 1;
+    if (fct == fasp_precond_ilu_backward) return 2;
+    return -1;
+}
+
+void ilu_precond_host(const char* fn, int which, double* r, double* z, void* data)
+{
+    ILU_data* d = static_cast<ILU_data*>(data);
+    if (ctx_init() < 0) die_no_device(fn);
+    const int m = d ? d->row : 0;
+    if (!d || d->nwork < 2 * m) {
+        std::printf("### ERROR: Need %d memory, only %d available!\n", 2 * m, d ? d->nwork : 0);
+        std::exit(ERROR_ALLOC_MEM);
+    }
+    std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
+    int st;
+    IluDev* D = ilu_device_of(d, tmp, &st);
+    if (D) {
+        st = hipMemcpyAsync(D->r, r, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
+        if (st >= 0) st = ilu_apply(D, which, D->r, D->z);
+        if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) st = ERROR_MISC;
+        if (st >= 0) st = seq_err_check();
+        if (st >= 0 && hipMemcpy(z, D->z, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess) st = ERROR_MISC;
+    }
+    if (st < 0) {
+        std::fprintf(stderr, "### ERROR: %s: device ILU application failed (%d)\n", fn, st);
+        std::exit(st);
+    }
+}
+
+// Krylov plug-in: the preconditioner as a device operation (nullptr: pc is not an ILU preconditioner).  *tmp owns a
+// per-solve copy; *st < 0: an ILU preconditioner that cannot be applied here.
+IluDev* ilu_of_precond(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* which, int* st)
+{
+    *st = FASP_SUCCESS;
+    if (!pc || !pc->data || !pc->fct) return nullptr;
+    *which = ilu_which(pc->fct);
+    if (*which < 0) return nullptr;
+    ILU_data* d = static_cast<ILU_data*>(pc->data);
+    if (d->row != n) { *st = ERROR_INPUT_PAR; return nullptr; }
+    return ilu_device_of(d, tmp, st);
+}
+}  // namespace
+
+namespace fasp {
+void ilu_register_host(ILU_data* d)
+{
+    FASP_ENTRY();
+    IluEntry* e = ilu_entry(d);
+    if (e) { ilu_dev_destroy(e->dev); e->dev = nullptr; return; }   // set up again: the old device copy is stale
+    g_ilu_registry.push_back(IluEntry{d, nullptr});
+}
+}  // namespace fasp
+
+}  // extern "C++"
+
+void fasp_precond_ilu(double* r, double* z, void* data)
+{
+    FASP_ENTRY();
+    ilu_precond_host(__func__, 0, r, z, data);
+}
+void fasp_precond_ilu_forward(double* r, double* z, void* data)
+{
+    FASP_ENTRY();
+    ilu_precond_host(__func__, 1, r, z, data);
+}
+void fasp_precond_ilu_backward(double* r, double* z, void* data)
+{
+    FASP_ENTRY();
+    ilu_precond_host(__func__, 2, r, z, data);
+}
+
+
+// PreDataInit.c:445.  ILUtp: the columns of the matrix the factor was made of are numbered back (iperm is 1-based).
+void fasp_ilu_data_free(ILU_data* iludata)
+{
+    FASP_ENTRY();
+    if (!iludata) return;
+    for (size_t q = 0; q < g_ilu_registry.size(); ++q)
+        if (g_ilu_registry[q].d == iludata) {
+            ilu_dev_destroy(g_ilu_registry[q].dev);
+            g_ilu_registry.erase(g_ilu_registry.begin() + (long)q);
+            break;
+        }
+    std::free(iludata->ijlu); iludata->ijlu = nullptr;
+    std::free(iludata->luval); iludata->luval = nullptr;
+    std::free(iludata->work); iludata->work = nullptr;
+    std::free(iludata->ilevL); iludata->ilevL = nullptr;
+    std::free(iludata->jlevL); iludata->jlevL = nullptr;
+    std::free(iludata->ilevU); iludata->ilevU = nullptr;
+    std::free(iludata->jlevU); iludata->jlevU = nullptr;
+    if (iludata->type == ILUtp) {
+        if (iludata->A) {
+            const int nnz = iludata->A->nnz;
+            const int* iperm = iludata->iperm;
+            for (int k = 0; k < nnz; ++k) iludata->A->JA[k] = iperm[iludata->A->JA[k]] - 1;
+        }
+        std::free(iludata->iperm); iludata->iperm = nullptr;
+    }
+}
+
+// device factors resident now (test entry, fasp_hip_dev.h)
+int fasp_hip_ilu_resident_count(void)
+{
+    FASP_ENTRY();
+    int c = 0;
+    for (const IluEntry& e : g_ilu_registry) c += e.dev ? 1 : 0;
+    return c;
+}
+
+// measurement entry (fasp_hip_dev.h): microseconds per solve of one triangle of a factor (which: 1 L, 2 U), the factor kept
+// resident as a solve keeps it; info (may be NULL, 6 doubles) = {levels, single launch (1) or level launches (0), bytes moved
+// per solve, slab entries, actual entries, longest row}
+double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info)
+{
+    FASP_ENTRY();
+    if (!iludata || (which != 1 && which != 2) || reps <= 0) return -1.0;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
+    int st;
+    IluDev* D = ilu_device_of(iludata, tmp, &st);
+    if (!D) return -1.0;
+    const IluTri& T = which == 1 ? D->L : D->U;
+    const bool upper = which == 2;
+    std::vector<double> h((size_t)D->n);
+    for (int i = 0; i < D->n; ++i) h[(size_t)i] = std::sin(0.37 * i) + 0.1;
+    if (hipMemcpy(D->r, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return -1.0;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
+    if (ilu_tri_solve(D, T, upper, D->r, D->z) < 0) return -1.0;   // warm-up
+    (void)hipEventRecord(e0, g_ctx.stream);
+    for (int i = 0; i < reps; ++i) (void)ilu_tri_solve(D, T, upper, D->r, D->z);
+    (void)hipEventRecord(e1, g_ctx.stream);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (seq_err_check() < 0) return -1.0;
+    if (info) {
+        const bool single = ilu_single_launch(T);
+        const double slots = 64.0 * T.nchunk;
+        // slots: row + length (+ the multiplier); slab: column + value; the gathered operands; rhs read, result written
+        // (+ the sentinel fill of the single launch)
+        const double bytes = slots * (upper ? 16.0 : 8.0) + 8.0 * T.nchunk + 12.0 * (double)T.nent + 8.0 * (double)T.nreal +
+                             16.0 * D->n + (single ? 8.0 * D->n : 0.0);
+        info[0] = T.nlev; info[1] = single ? 1 : 0; info[2] = bytes; info[3] = (double)T.nent; info[4] = (double)T.nreal; info[5] = T.maxlen;
+    }
+    return 1000.0 * ms / reps;
+}
+
+// ItrSmootherCSR.c:1280: x = x + (LU)^-1 (b - A x)
+void fasp_smoother_dcsr_ilu(dCSRmat* A, dvector* b, dvector* x, void* data)
+{
+    FASP_ENTRY();
+    ILU_data* d = static_cast<ILU_data*>(data);
+    if (ctx_init() < 0) die_no_device(__func__);
+    const int m = A->row;
+    if (!d || d->nwork < 3 * m) {
+        std::printf("### ERROR: ILU needs %d memory, only %d available! [%s]\n", 3 * m, d ? d->nwork : 0, __func__);
+        std::exit(ERROR_ALLOC_MEM);
+    }
+    if (d->row != m || A->col != m || b->row < m || x->row < m) {
+        std::fprintf(stderr, "### ERROR: %s: inconsistent arguments\n", __func__);
+        std::exit(ERROR_INPUT_PAR);
+    }
+    std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
+    int st;
+    IluDev* D = ilu_device_of(d, tmp, &st);
+    TmpCSR dA(A);
+    TmpVec db(b->val, (size_t)m), dx(x->val, (size_t)m);
+    if (D && (!dA.ok || !db.d || !dx.d)) st = ERROR_ALLOC_MEM;
+    if (D && st >= 0) {
+        d_resid(dA.D, dx.d, db.d, D->r);          // zr = b - A x
+        st = ilu_apply(D, 0, D->r, D->z);
+        if (st >= 0) d_axpy(m, 1.0, D->z, dx.d);  // x = x + 1 z
+        if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) st = ERROR_MISC;
+        if (st >= 0) st = seq_err_check();
+        if (st >= 0) dx.get(x->val);
+    }
+    if (st < 0) {
+        std::fprintf(stderr, "### ERROR: %s: device ILU smoother failed (%d)\n", __func__, st);
+        std::exit(st);
+    }
+}
+
+// SolCSR.c:588 / :668: ILU setup of A (or of M) + fasp_solver_dcsr_itsolver with fasp_precond_ilu (applied in HBM).  No device:
+// ERROR_MISC before any work; a partitioned run: ERROR_INPUT_PAR (one GPU, as the plug-in level).
+extern "C++" {
+namespace {
+int krylov_ilu_common(const char* label, dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam, dCSRmat* M)
+{
+    if (!A || !b || !x || !itparam || !iluparam || !M) return ERROR_INPUT_PAR;
+    if (ctx_init() < 0) {
+        std::fprintf(stderr, "### ERROR: %s: no usable HIP device and no CPU fallback in libfasp_hip\n", label);
+        return ERROR_MISC;
+    }
+    if (comm_size() > 1) return ERROR_INPUT_PAR;
+    const double t0 = wall_seconds();
+    ILU_data LU;
+    std::memset(&LU, 0, sizeof(LU));
+    int status = fasp_ilu_dcsr_setup(M, &LU, iluparam);
+    if (status >= 0) status = fasp_mem_iludata_check(&LU);
+    if (status >= 0) {
+        precond pc{&LU, fasp_precond_ilu};
+        status = fasp_solver_dcsr_itsolver(A, b, x, &pc, itparam);
+        if (itparam->print_level >= PRINT_MIN)
+            std::printf("%s_Krylov method%s costs %.4f seconds.\n",
+                        iluparam->ILU_type == ILUt ? "ILUt" : iluparam->ILU_type == ILUtp ? "ILUtp" : "ILUk", M == A ? " totally" : "",
+                        wall_seconds() - t0);
+    }
+    fasp_ilu_data_free(&LU);
+    return status;
+}
+}  // namespace
+}  // extern "C++"
+
+int fasp_solver_dcsr_krylov_ilu(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam)
+{
+    FASP_ENTRY();
+    return krylov_ilu_common(__func__, A, b, x, itparam, iluparam, A);
+}
+int fasp_solver_dcsr_krylov_ilu_M(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam, dCSRmat* M)
+{
+    FASP_ENTRY();
+    return krylov_ilu_common(__func__, A, b, x, itparam, iluparam, M);
+}

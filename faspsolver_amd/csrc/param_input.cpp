@@ -606,3 +606,21 @@ void fasp_fwrapper_dbsr_krylov_amg_(int* n, int* nnz, int* nb, int* ia, int* ja,
 }
 
 }  // extern "C"
+
+// SolWrapper.c:195: ILUk(2)-preconditioned VFGMRES (fasp_param_ilu_init / fasp_param_solver_init defaults) on the caller's arrays
+extern "C" void fasp_fwrapper_dcsr_krylov_ilu_(int* n, int* nnz, int* ia, int* ja, double* a, double* b, double* u, double* tol,
+                                               int* maxit, int* ptrlvl)
+{
+    ILU_param iluparam;
+    ITS_param itsparam;
+    fasp_param_ilu_init(&iluparam);
+    iluparam.print_level = (short)*ptrlvl;
+    fasp_param_solver_init(&itsparam);
+    itsparam.itsolver_type = SOLVER_VFGMRES;
+    itsparam.tol = *tol;
+    itsparam.maxit = *maxit;
+    itsparam.print_level = (short)*ptrlvl;
+    dCSRmat mat{*n, *n, *nnz, ia, ja, a};
+    dvector rhs{*n, b}, sol{*n, u};
+    fasp_solver_dcsr_krylov_ilu(&mat, &rhs, &sol, &itsparam, &iluparam);
+}

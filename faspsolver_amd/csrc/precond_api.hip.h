@@ -160,7 +160,6 @@ void fasp_amg_data_free(AMG_data* mgl, AMG_param* param)
 precond* fasp_precond_setup(const short precond_type, AMG_param* amgparam, ILU_param* iluparam, dCSRmat* A)
 {
     FASP_ENTRY();
-    (void)iluparam;
     if (precond_type == PREC_NULL) return nullptr;
     if (!A) { std::printf("### ERROR: fasp_precond_setup: A == NULL\n"); std::exit(ERROR_INPUT_PAR); }
     precond* pc = (precond*)fasp_mem_calloc(1, sizeof(precond));
@@ -175,8 +174,15 @@ precond* fasp_precond_setup(const short precond_type, AMG_param* amgparam, ILU_p
         pc->fct = fasp_precond_diag;
         return pc;
     }
+    if (precond_type == PREC_ILU) {  // PreCSR.c:130: the factor on the host (its status is not looked at), applied on the device
+        ILU_data* ilu = (ILU_data*)fasp_mem_calloc(1, sizeof(ILU_data));
+        fasp_ilu_dcsr_setup(A, ilu, iluparam);
+        pc->data = ilu;
+        pc->fct = fasp_precond_ilu;
+        return pc;
+    }
     if (precond_type != PREC_AMG && precond_type != PREC_FMG) {
-        std::printf("### ERROR: fasp_precond_setup: preconditioner type %d (ILU / Schwarz) has no device path in libfasp_hip\n",
+        std::printf("### ERROR: fasp_precond_setup: preconditioner type %d (Schwarz) has no device path in libfasp_hip\n",
                     (int)precond_type);
         std::exit(ERROR_SOLVER_PRECTYPE);
     }

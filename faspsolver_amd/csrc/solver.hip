@@ -1236,6 +1236,7 @@ precond* fasp_hip_precond_setup(dCSRmat* A, AMG_param* amgparam)
 }
 
 #include "precond_api.hip.h"
+#include "ilu.hip.h"
 
 void fasp_hip_precond_free(precond* pc)
 {
@@ -1288,8 +1289,15 @@ int krylov_plugin(const char* fn, int which, dCSRmat* A, dvector* b, dvector* u,
         return launch_csr<OP_MXV_DOT>(*dA, a);
     };
     std::unique_ptr<TmpVec> ddiag;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
+    int ilu_which_ = -1, ilu_st = FASP_SUCCESS;
+    IluDev* ilu = h ? nullptr : ilu_of_precond(pc, n, ilu_tmp, &ilu_which_, &ilu_st);
+    if (ilu_st < 0) return ilu_st;
     if (h) {
         K.pc = [h](double* in, double** out) { return precond_amg(h, in, out); };  // stays in HBM
+    } else if (ilu) {
+        // the reference's ILU preconditioner: recognised by its function pointer, both triangular solves on the device
+        K.pc = [ilu, ilu_which_](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, ilu_which_, in, ilu->z); };
     } else if (pc && pc->fct == fasp_precond_diag && pc->data && static_cast<dvector*>(pc->data)->row == n) {
         // the reference's diagonal preconditioner: recognised by its function pointer, applied on the device
         ddiag.reset(new TmpVec(static_cast<dvector*>(pc->data)->val, n));
@@ -1333,6 +1341,7 @@ int krylov_plugin(const char* fn, int which, dCSRmat* A, dvector* b, dvector* u,
         st = gmres_device(K, db.d, du.d, which == 2 ? 1 : which == 4 ? 3 : 0, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
     }
     du.get(u->val);
+    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
     for (double* q : ws) if (q) (void)hipFree(q);
     if (hh) (void)hipFree(hh);
     return st;
@@ -1749,8 +1758,14 @@ int krylov_matfree(const char* fn, int which, mxv_matfree* mf, dvector* b, dvect
     }
     fasp_hip_amg* h = (pc && pc->fct == fasp_hip_precond_fct) ? static_cast<fasp_hip_amg*>(pc->data) : nullptr;
     if (h && (h->L.empty() || h->L[0].A.row != n)) return ERROR_INPUT_PAR;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
+    int ilu_which_ = -1, ilu_st = FASP_SUCCESS;
+    IluDev* ilu = h ? nullptr : ilu_of_precond(pc, n, ilu_tmp, &ilu_which_, &ilu_st);
+    if (ilu_st < 0) return ilu_st;
     if (h) {
         K.pc = [h](double* in, double** out) { return precond_amg(h, in, out); };
+    } else if (ilu) {
+        K.pc = [ilu, ilu_which_](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, ilu_which_, in, ilu->z); };
     } else if (pc && pc->fct) {
         hr.resize((size_t)n); hz.resize((size_t)n);
         K.pc = [&, pc](double* in, double** out) {
@@ -1781,6 +1796,7 @@ int krylov_matfree(const char* fn, int which, mxv_matfree* mf, dvector* b, dvect
         default: st = ERROR_SOLVER_TYPE;
     }
     du.get(u->val);
+    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
     for (double* q : ws) if (q) (void)hipFree(q);
     if (hh) (void)hipFree(hh);
     return st;
@@ -2180,6 +2196,7 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "split_rows")) g_tune.split_rows = value;
     else if (!std::strcmp(key, "gs_multicolor")) g_tune.gs_multicolor = value;
     else if (!std::strcmp(key, "seq_flow")) { g_tune.seq_flow = value; if (value) g_flow_disabled = false; }
+    else if (!std::strcmp(key, "ilu_form")) g_tune.ilu_form = value;   // ILU triangular solves: -1 (default) by the schedule's depth, 0 one launch per level, 1 one launch
     else if (!std::strcmp(key, "seq_strip_kb")) g_tune.seq_strip_kb = value;   // KB of lower entries per strip of the dataflow solve (0, default: 256 / 512 / 1024 by level shape, seq_sched.cpp)
     else if (!std::strcmp(key, "seq_jobs")) g_tune.seq_jobs = value;
     else if (!std::strcmp(key, "local_square")) g_tune.local_square = value;   // a rank's rows of a partitioned level are coded like a square operator (read at upload)

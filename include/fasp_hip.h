@@ -59,6 +59,7 @@ extern "C" {
 #define ERROR_SOLVER_STAG     (-42)
 #define ERROR_SOLVER_SOLSTAG  (-43)
 #define ERROR_SOLVER_TOLSMALL (-44)
+#define ERROR_SOLVER_ILUSETUP (-45)
 #define ERROR_SOLVER_MISC     (-46)
 #define ERROR_SOLVER_MAXIT    (-48)
 #define ERROR_SOLVER_EXIT     (-49)
@@ -89,6 +90,8 @@ extern "C" {
 #define PREC_DIAG 1
 #define PREC_AMG  2
 #define PREC_FMG  3
+#define PREC_ILU     4
+#define PREC_SCHWARZ 5
 
 #define CLASSIC_AMG 1
 #define SA_AMG      2
@@ -133,6 +136,10 @@ extern "C" {
 #define VMB      2
 
 #define FASP_ILUk 1
+/* ILU_param.ILU_type (fasp_const.h:149-151) */
+#define ILUk  1
+#define ILUt  2
+#define ILUtp 3
 
 /* ------------------------------------------------------------------------ */
 /* types (serial layout of base/include/fasp.h; sizes checked in tests)     */
@@ -245,8 +252,9 @@ typedef struct {
 /* ---- reference-layout data of the AMG preconditioner (fasp.h:596-981, serial build without UMFPACK / MUMPS /
  * PARDISO / MULTI_COLOR_ORDER).  Field order and types are the reference's, so code compiled against fasp.h and
  * code compiled against this header agree on every offset (sizes pinned in tests/golden/abi.npz:
- * AMG_data 1104 bytes, precond_data 152 bytes).  ILU / Schwarz / direct-solver members are carried for layout
- * only: those smoothers and coarse solvers are out of scope here and stay zero. ---- */
+ * AMG_data 1104 bytes, precond_data 152 bytes).  ILU_param / ILU_data are those of the ILU preconditioner below
+ * (fasp_ilu_dcsr_setup); the ILU / Schwarz smoother and direct-solver members of AMG_data are carried for layout only:
+ * those smoothers and coarse solvers are out of scope here and stay zero. ---- */
 typedef struct {            /* fasp.h:404  ILU_param */
     short  print_level;
     short  ILU_type;
@@ -550,7 +558,8 @@ int fasp_hip_amg_solve(fasp_hip_amg* h, const dvector* b, dvector* x, const AMG_
  * safeguards; SpMV, BLAS-1 and orthogonalisation run on the device.  pc == NULL: no
  * preconditioner.  pc->fct == fasp_hip_precond_fct: the whole iteration stays in HBM.
  * Any other pc->fct is called as a host function on host copies of r and z (one PCIe round
- * trip per application) -- e.g. a reference preconditioner (ILU, Schwarz) kept on the CPU. */
+ * trip per application) -- e.g. a reference preconditioner (Schwarz) kept on the CPU.  fasp_precond_ilu / _forward /
+ * _backward are recognised by their address and applied on the device (triangular solves in HBM). */
 int fasp_solver_dcsr_pcg(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol,
                          const double abstol, const int MaxIt, const short StopType, const short PrtLvl);
 int fasp_solver_dcsr_pbcgs(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol,
@@ -615,8 +624,9 @@ int fasp_solver_dcsr_pvfgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, c
  * fasp_precond_setup (PreCSR.c:46): PREC_AMG / PREC_FMG build the hierarchy on the host, upload it, and hand out
  * precond{data = precond_data*, fct = fasp_precond_amg | _amli | _namli | _famg}; mgl_data[l].A / P / R / cfmark show
  * the host hierarchy (read-only views owned by the library), b / x / w are allocated as the reference's setup
- * leaves them.  PREC_DIAG gives fasp_precond_diag on a copy of the diagonal, PREC_NULL returns NULL; PREC_ILU /
- * PREC_SCHWARZ are out of scope: message + exit, as fasp_chkerr does.
+ * leaves them.  PREC_DIAG gives fasp_precond_diag on a copy of the diagonal, PREC_ILU gives
+ * precond{data = ILU_data*, fct = fasp_precond_ilu} from fasp_ilu_dcsr_setup (PreCSR.c:130), PREC_NULL returns NULL;
+ * PREC_SCHWARZ is out of scope: message + exit, as fasp_chkerr does.
  * fasp_precond_amg (PreCSR.c:416): z = B r for host vectors r, z -- pcdata->maxit cycles from a zero guess, cycle /
  * smoother parameters re-read from pcdata at every call (fasp_param_prec_to_amg).  Handed to this library's Krylov
  * methods these functions are recognised by their address and the whole iteration stays in HBM.
@@ -647,6 +657,34 @@ void fasp_smoother_dcsr_gs(dvector* u, const int i_1, const int i_n, const int s
 void fasp_smoother_dcsr_sor(dvector* u, const int i_1, const int i_n, const int s, dCSRmat* A, dvector* b, int L,
                             const double w);
 void fasp_smoother_dcsr_L1diag(dvector* u, const int i_1, const int i_n, const int s, dCSRmat* A, dvector* b, int L);
+
+/* ---- ILU preconditioner (BlaILUSetupCSR.c, PreCSR.c:198-360, SolCSR.c:588/:668) ----
+ * fasp_ilu_dcsr_setup: ILUk / ILUt / ILUtp factorisation on the HOST, output equal to the reference's entry for entry
+ * (MSR factor in ijlu / luval, luval[i] = inverse pivot, nzlu, iperm, work, status ERROR_SOLVER_ILUSETUP on failure).
+ * ILUtp renumbers the columns of A->JA in place, as the reference does; fasp_ilu_data_free renumbers them back.
+ * fasp_param_ilu_init, fasp_ilu_data_create, fasp_mem_iludata_check need no GPU either.
+ * fasp_precond_ilu / _forward / _backward: z = (LU)^-1 r, L^-1 r, U^-1 r for host vectors, computed on the device by
+ * level-scheduled triangular solves with the reference's order of operations (bit for bit the same z).  A factor made
+ * by fasp_ilu_dcsr_setup is uploaded at its first application and stays resident until fasp_ilu_data_free; any other
+ * ILU_data is uploaded for each call.  Without a device they refuse to run (no CPU fallback).
+ * fasp_solver_dcsr_krylov_ilu(_M): setup (of A, or of M) + fasp_solver_dcsr_itsolver with that preconditioner, every
+ * itsolver_type; the preconditioner stays in HBM.  fasp_smoother_dcsr_ilu (ItrSmootherCSR.c:1280): x += (LU)^-1 (b - A x).
+ * ILU as an AMG smoother (ILU_levels > 0), block / structured ILU and Schwarz stay out of scope. */
+void  fasp_param_ilu_init(ILU_param* iluparam);                                     /* AuxParam.c:595 */
+void  fasp_ilu_data_create(const int iwk, const int nwork, ILU_data* iludata);      /* PreDataInit.c:411 */
+void  fasp_ilu_data_free(ILU_data* iludata);                                        /* PreDataInit.c:445 */
+short fasp_mem_iludata_check(const ILU_data* iludata);                              /* AuxMemory.c:203 */
+short fasp_ilu_dcsr_setup(dCSRmat* A, ILU_data* iludata, ILU_param* iluparam);      /* BlaILUSetupCSR.c:40 */
+void  fasp_precond_ilu(double* r, double* z, void* data);                           /* PreCSR.c:198 */
+void  fasp_precond_ilu_forward(double* r, double* z, void* data);                   /* PreCSR.c:263 */
+void  fasp_precond_ilu_backward(double* r, double* z, void* data);                  /* PreCSR.c:317 */
+int   fasp_solver_dcsr_krylov_ilu(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam);
+int   fasp_solver_dcsr_krylov_ilu_M(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam,
+                                    dCSRmat* M);
+void  fasp_smoother_dcsr_ilu(dCSRmat* A, dvector* b, dvector* x, void* data);
+/* SolWrapper.c:195: ILUk(2)-preconditioned VFGMRES on a caller's CSR arrays (Fortran calling convention) */
+void  fasp_fwrapper_dcsr_krylov_ilu_(int* n, int* nnz, int* ia, int* ja, double* a, double* b, double* u,
+                                     double* tol, int* maxit, int* ptrlvl);
 
 /* The AMG preconditioner as a `precond` -- the role of fasp_precond_setup(PREC_AMG, ..)
  * (PreCSR.c:46) + fasp_precond_amg (PreCSR.c:416).  The returned object can be handed to the

@@ -41,6 +41,14 @@ double fasp_hip_seq_chain_selftest(const dCSRmat* A, const int* seq, int ns, int
  * triad over buffers of `bytes` each (>= 512 MiB: beyond the Infinity Cache) */
 int fasp_hip_measure_ceilings(double* out, size_t bytes, int reps);
 
+/* ILU triangular solves (csrc/ilu.hip.h).  fasp_hip_ilu_resident_count: factors made by fasp_ilu_dcsr_setup whose device copy
+ * is alive (uploaded at the first application, released by fasp_ilu_data_free).  fasp_hip_ilu_time: microseconds per solve
+ * of one triangle (which: 1 = L, 2 = U) on the device copy, averaged over `reps` back-to-back solves after one warm-up; info
+ * (may be NULL, 6 doubles) = {dependency levels, form (1 single launch, 0 level launches), bytes moved per solve, slab
+ * entries (padded), entries, longest row}; < 0: error. */
+int    fasp_hip_ilu_resident_count(void);
+double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
+
 /* Run-time switches (A/B tests, profiling, and ONE behavioural mode):
  *   kernel selection / launch geometry: maxgrid, xcd, nt, kind, lanes, wrows, wcap (-1 = automatic), gen2 (0 round-1
  *     kernels, 1, 2 = default), compress (lossless matrix coding on/off), ja16, ws2_bpc, rpl, lds_tab, xcd_pat, rp_strip (coded operators
@@ -68,6 +76,8 @@ int fasp_hip_measure_ceilings(double* out, size_t bytes, int reps);
  *     gs_multicolor = 1 selects the MULTICOLOUR Gauss-Seidel / SOR sweep -- NOT the reference's iteration (rows are
  *     relaxed colour by colour instead of in index order; faster, converges alike, other iteration counts). Default 0:
  *     the reference's sequential sweep, reproduced exactly;
+ *   ILU preconditioner: ilu_form (the triangular solves of fasp_precond_ilu and its kin: -1 (default) one launch for schedules
+ *     deeper than 24 levels, else one launch per level; 0 always one launch per level; 1 always one launch) -- same bits;
  *   multi-GPU: halo_overlap (exchange beside the interior rows, default 1), split_rows (test mode: every operator in
  *     three row windows), seq_partition (set before the upload, or FASP_HIP_SEQ_PARTITION=1: hierarchies with Gauss-Seidel / SOR
  *     smoothers are row-partitioned too and the ranks sweep by turns; default 0: such hierarchies keep every level whole),
