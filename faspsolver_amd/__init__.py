@@ -54,6 +54,8 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_precond_ilu", "fasp_precond_ilu_forward", "fasp_precond_ilu_backward", "fasp_solver_dcsr_krylov_ilu",
     "fasp_solver_dcsr_krylov_ilu_M", "fasp_smoother_dcsr_ilu", "fasp_fwrapper_dcsr_krylov_ilu_",
     "fasp_hip_ilu_resident_count", "fasp_hip_ilu_time",
+    "fasp_ilu_dbsr_setup", "fasp_precond_dbsr_ilu", "fasp_solver_dbsr_krylov_ilu", "fasp_smoother_dbsr_ilu",
+    "fasp_fwrapper_dbsr_krylov_ilu_",
 ]
 
 
@@ -227,7 +229,39 @@ def lib():
     L.fasp_fwrapper_dcsr_krylov_ilu_.restype = None
     L.fasp_hip_ilu_time.argtypes = [P(T.ILU_data), C.c_int, C.c_int, T.c_double_p]
     L.fasp_hip_ilu_time.restype = C.c_double
+    # block ILU (csrc/ilu_setup.cpp, csrc/ilu.hip.h)
+    L.fasp_ilu_dbsr_setup.argtypes = [P(T.dBSRmat), P(T.ILU_data), P(T.ILU_param)]
+    L.fasp_ilu_dbsr_setup.restype = C.c_short
+    L.fasp_precond_dbsr_ilu.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_dbsr_ilu.restype = None
+    L.fasp_solver_dbsr_krylov_ilu.argtypes = [P(T.dBSRmat), P(T.dvector), P(T.dvector), P(T.ITS_param), P(T.ILU_param)]
+    L.fasp_solver_dbsr_krylov_ilu.restype = C.c_int
+    L.fasp_smoother_dbsr_ilu.argtypes = [P(T.dBSRmat), P(T.dvector), P(T.dvector), C.c_void_p]
+    L.fasp_smoother_dbsr_ilu.restype = None
+    L.fasp_fwrapper_dbsr_krylov_ilu_.argtypes = [P(C.c_int), P(C.c_int), P(C.c_int), T.c_int_p, T.c_int_p, T.c_double_p,
+                                                 T.c_double_p, T.c_double_p, P(C.c_double), P(C.c_int), P(C.c_int)]
+    L.fasp_fwrapper_dbsr_krylov_ilu_.restype = None
     return L
+
+
+def solve_bsr_ilu(ia, ja, val, nb, b, x0=None, solver=None, tol=1e-8, maxit=500, lfil=0, print_level=0):
+    """fasp_solver_dbsr_krylov_ilu on numpy arrays (BSR, row-major nb x nb blocks): block ILUk(lfil) set up on the host,
+    the Krylov method (default BiCGstab) and both block triangular solves on the device.  Returns (status, x)."""
+    L = lib()
+    ia = np.ascontiguousarray(ia, dtype=np.int32); ja = np.ascontiguousarray(ja, dtype=np.int32)
+    val = np.ascontiguousarray(val, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.zeros(len(b)) if x0 is None else np.array(x0, dtype=np.float64)
+    A = T.dBSRmat()
+    A.ROW = A.COL = len(ia) - 1; A.NNZ = len(ja); A.nb = nb; A.storage_manner = 0
+    A.IA = ia.ctypes.data_as(T.c_int_p); A.JA = ja.ctypes.data_as(T.c_int_p); A.val = val.ctypes.data_as(T.c_double_p)
+    bv = T.dvector(len(b), b.ctypes.data_as(T.c_double_p)); xv = T.dvector(len(x), x.ctypes.data_as(T.c_double_p))
+    it = T.ITS_param(); L.fasp_param_solver_init(C.byref(it))
+    it.itsolver_type = T.SOLVER_BiCGstab if solver is None else solver
+    it.tol, it.maxit, it.print_level = tol, maxit, print_level
+    prm = T.ILU_param(); L.fasp_param_ilu_init(C.byref(prm))
+    prm.ILU_lfil, prm.print_level = lfil, print_level
+    st = L.fasp_solver_dbsr_krylov_ilu(C.byref(A), C.byref(bv), C.byref(xv), C.byref(it), C.byref(prm))
+    return st, x
 
 
 def available():

@@ -192,6 +192,9 @@ struct HostHierarchyBSR {
 int host_setup_ua_bsr(const dBSRmat* A, AMG_param* param, HostHierarchyBSR& H);
 // inverse diagonal blocks (BlaSparseBSR.c:543 -> fasp_smat_inv): closed forms for nb = 2, 3, 4, pivoting Gauss-Jordan for 5..7
 int bsr_diaginv(const dBSRmat* A, double* out);
+// fasp_smat_invp_nc (BlaSmallMatInv.c:508): one n x n block (n <= 8) inverted in place by pivoting Gauss-Jordan;
+// ERROR_SOLVER_EXIT on a pivot below SMALLREAL
+int smat_invp(double* a, int n);
 int check_supported_bsr(const ITS_param* itparam, const AMG_param* amgparam, int nb);
 
 // Parameter screening: every AMG_param / ITS_param combination without a device

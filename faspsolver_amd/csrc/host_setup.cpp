@@ -2324,6 +2324,8 @@ int bsr_diaginv(const dBSRmat* A, double* out)
     return FASP_SUCCESS;
 }
 
+int smat_invp(double* a, int n) { return block_inv_pivot(a, n); }
+
 int host_setup_ua_bsr(const dBSRmat* A, AMG_param* param, HostHierarchyBSR& H)
 {
     HostThreads team;  // bounded, constant team size for every parallel loop below

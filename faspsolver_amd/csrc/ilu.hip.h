@@ -23,6 +23,9 @@
 //                    then the error word, the solve fails loudly and later solves use level launches).
 // The form follows the schedule's depth (single launch beyond ILU_FLOW_MIN_LEVELS levels); fasp_hip_tune("ilu_form", 0 / 1)
 // forces one.  ILU(0) of P7(n) has 3 n - 2 levels per triangle: 766 at 256^3.
+//
+// Block factors (fasp_ilu_dbsr_setup, PreBSR.c:347) run through the same schedule with NB x NB blocks per entry (the kernels
+// are templated on NB, NB = 1 being the scalar factor): see ilu_chunk for the slab layout and the order of operations.
 
 #ifndef ILU_FLOW_MIN_LEVELS
 #define ILU_FLOW_MIN_LEVELS 24
@@ -43,50 +46,85 @@ struct IluArgs {
     int              nchunk;
 };
 
-template <bool HAS_D, bool SPIN>
+// one row of an NB x NB block times NB values, the row's elements 64 doubles apart (one slab plane each), summed left to
+// right as fasp_blas_smat_mxv does; NB = 6 has no unrolled form there and starts from 0.0 (its default branch)
+template <int NB>
+__device__ __forceinline__ double ilu_block_row(const double* a, const double* x)
+{
+    double m = NB == 6 ? 0.0 + a[0] * x[0] : a[0] * x[0];
+#pragma unroll
+    for (int q = 1; q < NB; ++q) m = m + a[64 * q] * x[q];
+    return m;
+}
+
+// One chunk of 64 (block) rows, one row per lane.  NB = 1: the scalar factor.  NB > 1: entry k of the chunk's rows is
+// an NB x NB block whose element (p, q) lies at vals[(cbase + 64 k) NB^2 + (p NB + q) 64 + lane] (NB^2 planes, each one
+// coalesced wavefront load); U's inverse diagonal blocks lie in NB^2 planes of 64 per chunk the same way.  Per entry the
+// lane forms mult_p = (L_ij x_j)_p and subtracts it, acc_p = acc_p - mult_p (PreBSR.c:347); U ends with z = D^-1 acc.
+template <int NB, bool HAS_D, bool SPIN>
 __device__ __forceinline__ void ilu_chunk(const IluArgs& a, int c, int lane)
 {
     typedef __attribute__((address_space(1))) unsigned long long gu64;
+    constexpr int NB2 = NB * NB;
     const int s = c * 64 + lane;
     const int row = a.rows[s];
     if (row < 0) return;
     const int len = a.len[s];
     const long long e0 = a.cbase[c] + lane;
-    double acc = a.in[row];
+    const double* v = a.vals + a.cbase[c] * NB2 + lane;
+    double acc[NB];
+#pragma unroll
+    for (int p = 0; p < NB; ++p) acc[p] = a.in[(long long)row * NB + p];
     unsigned spins = 0;
     unsigned long long t0 = 0;
     for (int k = 0; k < len; ++k) {
-        const int col = a.cols[e0 + 64ll * k];
-        const double v = a.vals[e0 + 64ll * k];
-        double x;
-        if (SPIN) {
-            unsigned long long bits = __hip_atomic_load((gu64*)(a.out + col), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            while (bits == ~0ull) {
-                if (flow_give_up(a.sync, spins, t0)) break;
-                __builtin_amdgcn_s_sleep(1);
-                bits = __hip_atomic_load((gu64*)(a.out + col), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const long long col = a.cols[e0 + 64ll * k];
+        double x[NB];
+#pragma unroll
+        for (int q = 0; q < NB; ++q) {
+            if (SPIN) {   // each component is its own flag
+                gu64* src = (gu64*)(a.out + col * NB + q);
+                unsigned long long bits = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                while (bits == ~0ull) {
+                    if (flow_give_up(a.sync, spins, t0)) break;
+                    __builtin_amdgcn_s_sleep(1);
+                    bits = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                x[q] = __longlong_as_double((long long)bits);
+            } else {
+                x[q] = a.out[col * NB + q];
             }
-            x = __longlong_as_double((long long)bits);
-        } else {
-            x = a.out[col];
         }
-        acc = acc - v * x;
+        const double* vk = v + 64ll * NB2 * k;
+#pragma unroll
+        for (int p = 0; p < NB; ++p) acc[p] = acc[p] - ilu_block_row<NB>(vk + 64 * NB * p, x);
     }
-    if (HAS_D) acc = acc * a.diag[s];
-    if (SPIN) __hip_atomic_store((gu64*)(a.out + row), (unsigned long long)__double_as_longlong(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else a.out[row] = acc;
+    if (HAS_D) {
+        const double* dk = a.diag + (long long)c * NB2 * 64 + lane;
+        double z[NB];
+#pragma unroll
+        for (int p = 0; p < NB; ++p) z[p] = NB == 1 ? acc[0] * dk[0] : ilu_block_row<NB>(dk + 64 * NB * p, acc);
+#pragma unroll
+        for (int p = 0; p < NB; ++p) acc[p] = z[p];
+    }
+#pragma unroll
+    for (int p = 0; p < NB; ++p) {
+        double* dst = a.out + (long long)row * NB + p;
+        if (SPIN) __hip_atomic_store((gu64*)dst, (unsigned long long)__double_as_longlong(acc[p]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *dst = acc[p];
+    }
 }
 
 // one level: chunks [c0, c1), four wavefronts per workgroup, one chunk each
-template <bool HAS_D>
+template <int NB, bool HAS_D>
 __global__ __launch_bounds__(256) void k_ilu_level(IluArgs a, int c0, int c1)
 {
     const int c = c0 + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (c < c1) ilu_chunk<HAS_D, false>(a, c, (int)(threadIdx.x & 63));
+    if (c < c1) ilu_chunk<NB, HAS_D, false>(a, c, (int)(threadIdx.x & 63));
 }
 
 // all levels in one launch: wavefronts draw chunks in level order
-template <bool HAS_D>
+template <int NB, bool HAS_D>
 __global__ __launch_bounds__(256) void k_ilu_flow(IluArgs a)
 {
     typedef __attribute__((address_space(1))) unsigned gu32;
@@ -96,7 +134,7 @@ __global__ __launch_bounds__(256) void k_ilu_flow(IluArgs a)
         if (lane == 0) c = (int)__hip_atomic_fetch_add((gu32*)a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         c = __shfl(c, 0);
         if (c >= a.nchunk) break;
-        ilu_chunk<HAS_D, true>(a, c, lane);
+        ilu_chunk<NB, HAS_D, true>(a, c, lane);
     }
 }
 
@@ -112,7 +150,7 @@ struct IluTri {
     double *vals = nullptr, *diag = nullptr;
 };
 struct IluDev {
-    int      n = 0;
+    int      n = 0, nb = 1;   // (block) rows, block size (1: a scalar factor, or a block factor with nb = 1)
     IluTri   L, U;
     double  *y = nullptr, *r = nullptr, *z = nullptr;
     unsigned* sync = nullptr;
@@ -154,7 +192,7 @@ void ilu_row_entries(const ILU_data* d, int i, bool upper, std::vector<int>& pos
 
 int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
 {
-    const int n = d->row;
+    const int n = d->row, nb2 = D->nb * D->nb;
     std::vector<int> level((size_t)n, 0), pos;
     int nlev = 0;
     for (int t = 0; t < n; ++t) {
@@ -186,7 +224,7 @@ int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
     const size_t nslot = (size_t)T.nchunk * 64;
     std::vector<int> rows(nslot, -1), len(nslot, 0);
     std::vector<long long> cbase((size_t)T.nchunk, 0);
-    std::vector<double> diag(upper ? nslot : 0, 0.0);
+    std::vector<double> diag(upper ? nslot * nb2 : 0, 0.0);   // NB^2 planes of 64 per chunk
     long long nent = 0;
     T.maxlen = 0; T.nreal = 0;
     for (int l = 0; l < nlev; ++l)
@@ -199,7 +237,8 @@ int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
                 ilu_row_entries(d, i, upper, pos);
                 rows[(size_t)c * 64 + lane] = i;
                 len[(size_t)c * 64 + lane] = (int)pos.size();
-                if (upper) diag[(size_t)c * 64 + lane] = d->luval[i];
+                if (upper)
+                    for (int e = 0; e < nb2; ++e) diag[((size_t)c * nb2 + e) * 64 + lane] = d->luval[(size_t)i * nb2 + e];
                 kmax = std::max(kmax, (int)pos.size());
                 T.nreal += (long long)pos.size();
             }
@@ -209,7 +248,7 @@ int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
         }
     T.nent = nent;
     std::vector<int> cols((size_t)nent, 0);
-    std::vector<double> vals((size_t)nent, 0.0);
+    std::vector<double> vals((size_t)nent * nb2, 0.0);   // entry k, element el of a slot: ((cbase + 64 k) nb2 + el) 64 + lane
     for (int c = 0; c < T.nchunk; ++c)
         for (int lane = 0; lane < 64; ++lane) {
             const int i = rows[(size_t)c * 64 + lane];
@@ -218,7 +257,8 @@ int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
             for (size_t k = 0; k < pos.size(); ++k) {
                 const size_t e = (size_t)cbase[(size_t)c] + 64 * k + (size_t)lane;
                 cols[e] = d->ijlu[pos[k]];
-                vals[e] = d->luval[pos[k]];
+                const size_t v0 = ((size_t)cbase[(size_t)c] + 64 * k) * nb2 + (size_t)lane;
+                for (int el = 0; el < nb2; ++el) vals[v0 + 64 * (size_t)el] = d->luval[(size_t)pos[k] * nb2 + el];
             }
         }
     if (!ilu_put(D, &T.rows, rows, nslot) || !ilu_put(D, &T.len, len, nslot) || !ilu_put(D, &T.cbase, cbase, cbase.size()) ||
@@ -228,20 +268,22 @@ int ilu_build_tri(IluDev* D, const ILU_data* d, bool upper, IluTri& T)
     return FASP_SUCCESS;
 }
 
-// the device copy of a factor (nullptr: no device, or an inconsistent factor -- *st says which)
-IluDev* ilu_upload(const ILU_data* d, int* st)
+// the device copy of a factor with nb x nb blocks (nullptr: no device, or an inconsistent factor -- *st says which)
+IluDev* ilu_upload(const ILU_data* d, int nb, int* st)
 {
     *st = FASP_SUCCESS;
     if (ctx_init() < 0) { *st = ERROR_MISC; return nullptr; }
-    if (!d || d->row <= 0 || !d->ijlu || !d->luval) { *st = ERROR_INPUT_PAR; return nullptr; }
+    if (!d || d->row <= 0 || !d->ijlu || !d->luval || nb < 1 || nb > 7) { *st = ERROR_INPUT_PAR; return nullptr; }
     IluDev* D = new IluDev;
     D->n = d->row;
+    D->nb = nb;
+    const size_t len = (size_t)D->n * nb;
     const std::vector<double> none;
     const std::vector<unsigned> sync0(16, 0u);
     int e = ilu_build_tri(D, d, false, D->L);
     if (e == FASP_SUCCESS) e = ilu_build_tri(D, d, true, D->U);
-    if (e == FASP_SUCCESS && (!ilu_put(D, &D->y, none, (size_t)D->n) || !ilu_put(D, &D->r, none, (size_t)D->n) ||
-                              !ilu_put(D, &D->z, none, (size_t)D->n) || !ilu_put(D, &D->sync, sync0, sync0.size())))
+    if (e == FASP_SUCCESS && (!ilu_put(D, &D->y, none, len) || !ilu_put(D, &D->r, none, len) ||
+                              !ilu_put(D, &D->z, none, len) || !ilu_put(D, &D->sync, sync0, sync0.size())))
         e = ERROR_ALLOC_MEM;
     if (e == FASP_SUCCESS) {
         const unsigned long long herr_addr = (unsigned long long)seq_err_device_word();
@@ -258,26 +300,44 @@ bool ilu_single_launch(const IluTri& T)
     return T.nlev > ILU_FLOW_MIN_LEVELS;
 }
 
-// out = T^-1 in (in, out: device vectors of n, not the same)
+template <int NB>
+void ilu_launch(const IluTri& T, bool upper, bool single, const IluArgs& a)
+{
+    if (single) {
+        const int grid = std::max(1, std::min((T.nchunk + 3) / 4, 1024));
+        if (upper) hipLaunchKernelGGL((k_ilu_flow<NB, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
+        else hipLaunchKernelGGL((k_ilu_flow<NB, false>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
+        return;
+    }
+    for (int l = 0; l < T.nlev; ++l) {
+        const int c0 = T.lvl_chunk[(size_t)l], c1 = T.lvl_chunk[(size_t)l + 1];
+        const dim3 grid((unsigned)((c1 - c0 + 3) / 4));
+        if (upper) hipLaunchKernelGGL((k_ilu_level<NB, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+        else hipLaunchKernelGGL((k_ilu_level<NB, false>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+    }
+}
+
+// out = T^-1 in (in, out: device vectors of n nb, not the same)
 int ilu_tri_solve(IluDev* D, const IluTri& T, bool upper, const double* in, double* out)
 {
     IluArgs a{};
     a.rows = T.rows; a.len = T.len; a.cbase = T.cbase; a.cols = T.cols; a.vals = T.vals; a.diag = T.diag;
     a.in = in; a.out = out; a.sync = D->sync; a.nchunk = T.nchunk;
     if (T.nchunk == 0) return FASP_SUCCESS;
-    if (ilu_single_launch(T)) {
-        HIPCK(hipMemsetAsync(out, 0xFF, sizeof(double) * (size_t)D->n, g_ctx.stream));   // the sentinel: not yet computed
-        HIPCK(hipMemsetAsync(D->sync, 0, 8, g_ctx.stream));                               // ticket counter + error word
-        const int grid = std::max(1, std::min((T.nchunk + 3) / 4, 1024));
-        if (upper) hipLaunchKernelGGL(k_ilu_flow<true>, dim3(grid), dim3(256), 0, g_ctx.stream, a);
-        else hipLaunchKernelGGL(k_ilu_flow<false>, dim3(grid), dim3(256), 0, g_ctx.stream, a);
-    } else {
-        for (int l = 0; l < T.nlev; ++l) {
-            const int c0 = T.lvl_chunk[(size_t)l], c1 = T.lvl_chunk[(size_t)l + 1];
-            const dim3 grid((unsigned)((c1 - c0 + 3) / 4));
-            if (upper) hipLaunchKernelGGL(k_ilu_level<true>, grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
-            else hipLaunchKernelGGL(k_ilu_level<false>, grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
-        }
+    const bool single = ilu_single_launch(T);
+    if (single) {
+        HIPCK(hipMemsetAsync(out, 0xFF, sizeof(double) * (size_t)D->n * D->nb, g_ctx.stream));   // the sentinel: not yet computed
+        HIPCK(hipMemsetAsync(D->sync, 0, 8, g_ctx.stream));                                       // ticket counter + error word
+    }
+    switch (D->nb) {
+        case 1: ilu_launch<1>(T, upper, single, a); break;
+        case 2: ilu_launch<2>(T, upper, single, a); break;
+        case 3: ilu_launch<3>(T, upper, single, a); break;
+        case 4: ilu_launch<4>(T, upper, single, a); break;
+        case 5: ilu_launch<5>(T, upper, single, a); break;
+        case 6: ilu_launch<6>(T, upper, single, a); break;
+        case 7: ilu_launch<7>(T, upper, single, a); break;
+        default: return ERROR_INPUT_PAR;
     }
     return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
 }
@@ -293,8 +353,10 @@ int ilu_apply(IluDev* D, int which, const double* in, double* out)
     return st < 0 ? st : ilu_tri_solve(D, D->U, true, D->y, out);
 }
 
-// factors made by fasp_ilu_dcsr_setup: device copy made at the first application, dropped by fasp_ilu_data_free
-struct IluEntry { ILU_data* d; IluDev* dev; };
+// factors made by fasp_ilu_dcsr_setup / fasp_ilu_dbsr_setup: device copy made at the first application, dropped by
+// fasp_ilu_data_free.  block_nb records the kind: 0 a scalar factor, else the block size of a block factor (ILU_data.nb
+// alone cannot tell: the scalar setup leaves it as the caller's struct held it).
+struct IluEntry { ILU_data* d; IluDev* dev; int block_nb; };
 std::vector<IluEntry> g_ilu_registry;
 
 IluEntry* ilu_entry(const ILU_data* d)
@@ -304,16 +366,20 @@ IluEntry* ilu_entry(const ILU_data* d)
     return nullptr;
 }
 
-// the device copy to apply `d` with: resident (registered factor) or made for this use (*tmp owns it)
-IluDev* ilu_device_of(ILU_data* d, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* st)
+// the device copy to apply `d` with: resident (a registered factor of the kind the entry point asks for) or made for
+// this use (*tmp owns it).  block: applied as a block factor (fasp_precond_dbsr_ilu and its kin), block size from the
+// registry's record, else from d->nb.
+IluDev* ilu_device_of(ILU_data* d, bool block, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* st)
 {
     *st = FASP_SUCCESS;
     IluEntry* e = ilu_entry(d);
-    if (e) {
-        if (!e->dev) e->dev = ilu_upload(d, st);
+    const bool same_kind = e && (e->block_nb > 0) == block;
+    const int nb = !block ? 1 : same_kind ? e->block_nb : (d ? d->nb : 0);
+    if (same_kind) {
+        if (!e->dev) e->dev = ilu_upload(d, nb, st);
         return e->dev;
     }
-    tmp.reset(ilu_upload(d, st));
+    tmp.reset(ilu_upload(d, nb, st));
     return tmp.get();
 }
 
@@ -325,18 +391,19 @@ int ilu_which(void (*fct)(double*, double*, void*))
     return -1;
 }
 
-void ilu_precond_host(const char* fn, int which, double* r, double* z, void* data)
+void ilu_precond_host(const char* fn, int which, bool block, double* r, double* z, void* data)
 {
     ILU_data* d = static_cast<ILU_data*>(data);
     if (ctx_init() < 0) die_no_device(fn);
-    const int m = d ? d->row : 0;
-    if (!d || d->nwork < 2 * m) {
-        std::printf("### ERROR: Need %d memory, only %d available!\n", 2 * m, d ? d->nwork : 0);
+    const int rows = d ? d->row : 0;
+    if (!d || d->nwork < 2 * rows) {
+        std::printf("### ERROR: Need %d memory, only %d available!\n", 2 * rows, d ? d->nwork : 0);
         std::exit(ERROR_ALLOC_MEM);
     }
     std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
     int st;
-    IluDev* D = ilu_device_of(d, tmp, &st);
+    IluDev* D = ilu_device_of(d, block, tmp, &st);
+    const int m = D ? D->n * D->nb : 0;
     if (D) {
         st = hipMemcpyAsync(D->r, r, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
         if (st >= 0) st = ilu_apply(D, which, D->r, D->z);
@@ -360,17 +427,27 @@ IluDev* ilu_of_precond(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluD
     if (*which < 0) return nullptr;
     ILU_data* d = static_cast<ILU_data*>(pc->data);
     if (d->row != n) { *st = ERROR_INPUT_PAR; return nullptr; }
-    return ilu_device_of(d, tmp, st);
+    return ilu_device_of(d, false, tmp, st);
+}
+
+// the same for the block Krylov plug-in: fasp_precond_dbsr_ilu, n = block rows * nb of the system
+IluDev* ilu_of_precond_bsr(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* st)
+{
+    *st = FASP_SUCCESS;
+    if (!pc || !pc->data || pc->fct != fasp_precond_dbsr_ilu) return nullptr;
+    IluDev* D = ilu_device_of(static_cast<ILU_data*>(pc->data), true, tmp, st);
+    if (D && D->n * D->nb != n) { *st = ERROR_INPUT_PAR; return nullptr; }
+    return D;
 }
 }  // namespace
 
 namespace fasp {
-void ilu_register_host(ILU_data* d)
+void ilu_register_host(ILU_data* d, int block_nb)
 {
     FASP_ENTRY();
     IluEntry* e = ilu_entry(d);
-    if (e) { ilu_dev_destroy(e->dev); e->dev = nullptr; return; }   // set up again: the old device copy is stale
-    g_ilu_registry.push_back(IluEntry{d, nullptr});
+    if (e) { ilu_dev_destroy(e->dev); e->dev = nullptr; e->block_nb = block_nb; return; }   // set up again: the old device copy is stale
+    g_ilu_registry.push_back(IluEntry{d, nullptr, block_nb});
 }
 }  // namespace fasp
 
@@ -379,17 +456,23 @@ void ilu_register_host(ILU_data* d)
 void fasp_precond_ilu(double* r, double* z, void* data)
 {
     FASP_ENTRY();
-    ilu_precond_host(__func__, 0, r, z, data);
+    ilu_precond_host(__func__, 0, false, r, z, data);
 }
 void fasp_precond_ilu_forward(double* r, double* z, void* data)
 {
     FASP_ENTRY();
-    ilu_precond_host(__func__, 1, r, z, data);
+    ilu_precond_host(__func__, 1, false, r, z, data);
 }
 void fasp_precond_ilu_backward(double* r, double* z, void* data)
 {
     FASP_ENTRY();
-    ilu_precond_host(__func__, 2, r, z, data);
+    ilu_precond_host(__func__, 2, false, r, z, data);
+}
+// PreBSR.c:347: z = (LU)^-1 r with a block factor (nb = 1: the scalar solves, whose arithmetic is the same)
+void fasp_precond_dbsr_ilu(double* r, double* z, void* data)
+{
+    FASP_ENTRY();
+    ilu_precond_host(__func__, 0, true, r, z, data);
 }
 
 
@@ -431,20 +514,22 @@ int fasp_hip_ilu_resident_count(void)
 }
 
 // measurement entry (fasp_hip_dev.h): microseconds per solve of one triangle of a factor (which: 1 L, 2 U), the factor kept
-// resident as a solve keeps it; info (may be NULL, 6 doubles) = {levels, single launch (1) or level launches (0), bytes moved
-// per solve, slab entries, actual entries, longest row}
+// resident as a solve keeps it (a block factor of fasp_ilu_dbsr_setup is applied as one); info (may be NULL, 6 doubles) =
+// {levels, single launch (1) or level launches (0), bytes moved per solve, slab entries, actual entries, longest row}
 double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info)
 {
     FASP_ENTRY();
     if (!iludata || (which != 1 && which != 2) || reps <= 0) return -1.0;
     std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
     int st;
-    IluDev* D = ilu_device_of(iludata, tmp, &st);
+    const IluEntry* e = ilu_entry(iludata);
+    IluDev* D = ilu_device_of(iludata, e && e->block_nb > 0, tmp, &st);
     if (!D) return -1.0;
     const IluTri& T = which == 1 ? D->L : D->U;
     const bool upper = which == 2;
-    std::vector<double> h((size_t)D->n);
-    for (int i = 0; i < D->n; ++i) h[(size_t)i] = std::sin(0.37 * i) + 0.1;
+    const size_t len = (size_t)D->n * D->nb;
+    std::vector<double> h(len);
+    for (size_t i = 0; i < len; ++i) h[i] = std::sin(0.37 * (double)i) + 0.1;
     if (hipMemcpy(D->r, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return -1.0;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
@@ -459,11 +544,11 @@ double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info)
     if (seq_err_check() < 0) return -1.0;
     if (info) {
         const bool single = ilu_single_launch(T);
-        const double slots = 64.0 * T.nchunk;
-        // slots: row + length (+ the multiplier); slab: column + value; the gathered operands; rhs read, result written
-        // (+ the sentinel fill of the single launch)
-        const double bytes = slots * (upper ? 16.0 : 8.0) + 8.0 * T.nchunk + 12.0 * (double)T.nent + 8.0 * (double)T.nreal +
-                             16.0 * D->n + (single ? 8.0 * D->n : 0.0);
+        const double slots = 64.0 * T.nchunk, nb = D->nb, nb2 = nb * nb, vec = (double)D->n * nb;
+        // slots: row + length (+ the inverse diagonal block); slab: column + block; the gathered operands; rhs read,
+        // result written (+ the sentinel fill of the single launch)
+        const double bytes = slots * (8.0 + (upper ? 8.0 * nb2 : 0.0)) + 8.0 * T.nchunk + (4.0 + 8.0 * nb2) * (double)T.nent +
+                             8.0 * nb * (double)T.nreal + 16.0 * vec + (single ? 8.0 * vec : 0.0);
         info[0] = T.nlev; info[1] = single ? 1 : 0; info[2] = bytes; info[3] = (double)T.nent; info[4] = (double)T.nreal; info[5] = T.maxlen;
     }
     return 1000.0 * ms / reps;
@@ -486,7 +571,7 @@ void fasp_smoother_dcsr_ilu(dCSRmat* A, dvector* b, dvector* x, void* data)
     }
     std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
     int st;
-    IluDev* D = ilu_device_of(d, tmp, &st);
+    IluDev* D = ilu_device_of(d, false, tmp, &st);
     TmpCSR dA(A);
     TmpVec db(b->val, (size_t)m), dx(x->val, (size_t)m);
     if (D && (!dA.ok || !db.d || !dx.d)) st = ERROR_ALLOC_MEM;
@@ -497,6 +582,43 @@ void fasp_smoother_dcsr_ilu(dCSRmat* A, dvector* b, dvector* x, void* data)
         if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) st = ERROR_MISC;
         if (st >= 0) st = seq_err_check();
         if (st >= 0) dx.get(x->val);
+    }
+    if (st < 0) {
+        std::fprintf(stderr, "### ERROR: %s: device ILU smoother failed (%d)\n", __func__, st);
+        std::exit(st);
+    }
+}
+
+// ItrSmootherBSR.c:1479: x = x + (LU)^-1 (b - A x) with a block factor; the work space check is the reference's (5 m)
+void fasp_smoother_dbsr_ilu(dBSRmat* A, dvector* b, dvector* x, void* data)
+{
+    FASP_ENTRY();
+    ILU_data* d = static_cast<ILU_data*>(data);
+    if (ctx_init() < 0) die_no_device(__func__);
+    const int m = d && A ? A->ROW * d->nb : 0;
+    if (!d || d->nwork < 5 * m) {
+        std::printf("### ERROR: ILU needs %d memory, only %d available! [%s]\n", 5 * m, d ? d->nwork : 0, __func__);
+        std::exit(ERROR_ALLOC_MEM);
+    }
+    std::unique_ptr<IluDev, void (*)(IluDev*)> tmp(nullptr, ilu_dev_destroy);
+    int st;
+    IluDev* D = ilu_device_of(d, true, tmp, &st);
+    if (D && (D->n != A->ROW || D->nb != A->nb || A->COL != A->ROW || b->row < m || x->row < m)) {
+        std::fprintf(stderr, "### ERROR: %s: inconsistent arguments\n", __func__);
+        std::exit(ERROR_INPUT_PAR);
+    }
+    if (D) {
+        TmpBSR dA(A);
+        TmpVec db(b->val, (size_t)m), dx(x->val, (size_t)m);
+        if (!dA.ok || !db.d || !dx.d) st = ERROR_ALLOC_MEM;
+        if (st >= 0) {
+            bsr_resid(dA, dx.d, db.d, D->r);          // zr = b - A x
+            st = ilu_apply(D, 0, D->r, D->z);
+            if (st >= 0) d_axpy(m, 1.0, D->z, dx.d);  // x = x + 1 z
+            if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) st = ERROR_MISC;
+            if (st >= 0) st = seq_err_check();
+            if (st >= 0) dx.get(x->val);
+        }
     }
     if (st < 0) {
         std::fprintf(stderr, "### ERROR: %s: device ILU smoother failed (%d)\n", __func__, st);
@@ -544,4 +666,30 @@ int fasp_solver_dcsr_krylov_ilu_M(dCSRmat* A, dvector* b, dvector* x, ITS_param*
 {
     FASP_ENTRY();
     return krylov_ilu_common(__func__, A, b, x, itparam, iluparam, M);
+}
+
+// SolBSR.c:286: block ILU setup + fasp_solver_dbsr_itsolver with fasp_precond_dbsr_ilu (applied in HBM by the block plug-in).
+// No device: ERROR_MISC before any work; a partitioned run: ERROR_INPUT_PAR.
+int fasp_solver_dbsr_krylov_ilu(dBSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam)
+{
+    FASP_ENTRY();
+    if (!A || !b || !x || !itparam || !iluparam) return ERROR_INPUT_PAR;
+    if (ctx_init() < 0) {
+        std::fprintf(stderr, "### ERROR: %s: no usable HIP device and no CPU fallback in libfasp_hip\n", __func__);
+        return ERROR_MISC;
+    }
+    if (comm_size() > 1) return ERROR_INPUT_PAR;
+    const double t0 = wall_seconds();
+    ILU_data LU;
+    std::memset(&LU, 0, sizeof(LU));
+    int status = fasp_ilu_dbsr_setup(A, &LU, iluparam);
+    if (status >= 0) status = fasp_mem_iludata_check(&LU);
+    if (status >= 0) {
+        precond pc{&LU, fasp_precond_dbsr_ilu};
+        status = fasp_solver_dbsr_itsolver(A, b, x, &pc, itparam);
+        if (itparam->print_level > PRINT_NONE)
+            std::printf("ILUk_Krylov method totally costs %.4f seconds\n", wall_seconds() - t0);
+    }
+    fasp_ilu_data_free(&LU);
+    return status;
 }

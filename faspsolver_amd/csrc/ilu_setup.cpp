@@ -24,7 +24,9 @@
 #include "fasp_internal.h"
 
 namespace fasp {
-void ilu_register_host(ILU_data* d);   // ilu.hip.h: factors built here are kept resident on the device once used
+// ilu.hip.h: factors built here are kept resident on the device once used.  block_nb: 0 for a factor of
+// fasp_ilu_dcsr_setup, the block size for one of fasp_ilu_dbsr_setup (the registry's record of the kind)
+void ilu_register_host(ILU_data* d, int block_nb);
 }
 
 namespace {
@@ -277,6 +279,149 @@ int factor_ilut(const dCSRmat* A, int n, int lfil, double droptol, double permto
     return FACT_OK;
 }
 
+// ---- block ILU(k) of a BSR matrix (BlaILUSetupBSR.c:55) ----
+// Symbolic pass (the level-of-fill pattern of the block pattern, BlaILU.c:1372).  Row i starts from the off-diagonal
+// columns of A's row i at level 0; its columns j < i are visited in ascending order (fill added on the way included), and
+// each U entry (c, s2) of row j offers column c at level s1 + s2 + 1 (s1: level of (i, j)): a new column is taken when
+// that level is <= lfil, an existing one keeps the smaller level.  The row is stored with ascending columns -- L entries,
+// then U entries -- and the diagonal block at position i.  Returns nzlu, or -1 when more than iwk entries are needed,
+// -2 for a row without its diagonal or with a repeated column.
+int bsr_symbolic(const dBSRmat* A, int lfil, int iwk, std::vector<int>& ijlu, std::vector<int>& uptr)
+{
+    const int n = A->ROW;
+    ijlu.assign((size_t)std::max(iwk, n + 1), 0);
+    uptr.assign((size_t)n, 0);
+    std::vector<int> level((size_t)std::max(iwk, n + 1), 0);   // level of each stored entry (position-indexed)
+    std::vector<int> next((size_t)n + 1, n), rowlev((size_t)n, 0), mark((size_t)n, -1), cols;
+    int nz = n + 1;
+    ijlu[0] = n + 1;
+    for (int i = 0; i < n; ++i) {
+        cols.clear();
+        bool diag = false;
+        for (int k = A->IA[i]; k < A->IA[i + 1]; ++k) {
+            const int c = A->JA[k];
+            if (c < 0 || c >= n || mark[(size_t)c] == i) return -2;
+            mark[(size_t)c] = i;
+            if (c == i) diag = true;
+            else { cols.push_back(c); rowlev[(size_t)c] = 0; }
+        }
+        if (!diag && !cols.empty()) return -2;
+        std::sort(cols.begin(), cols.end());
+        // the row as a sorted linked list: head -> next[] -> ... -> n
+        int head = n;
+        for (size_t q = cols.size(); q-- > 0;) { next[(size_t)cols[q]] = head; head = cols[q]; }
+        int lower = 0, count = (int)cols.size();
+        for (int j = head; j < i; j = next[(size_t)j]) {
+            ++lower;
+            if (lfil == 0) continue;
+            int prev = j;
+            const int s1 = rowlev[(size_t)j];
+            for (int m = uptr[(size_t)j]; m < ijlu[(size_t)j + 1]; ++m) {
+                const int c = ijlu[(size_t)m];
+                const int lev = s1 + level[(size_t)m] + 1;
+                if (mark[(size_t)c] != i) {
+                    if (lev > lfil) continue;
+                    mark[(size_t)c] = i;
+                    rowlev[(size_t)c] = lev;
+                    while (next[(size_t)prev] <= c) prev = next[(size_t)prev];   // U columns of row j ascend: insert after prev
+                    next[(size_t)c] = next[(size_t)prev];
+                    next[(size_t)prev] = c;
+                    prev = c;
+                    ++count;
+                } else if (c != i) {
+                    rowlev[(size_t)c] = std::min(rowlev[(size_t)c], lev);
+                }
+            }
+        }
+        if (nz + count > iwk) return -1;
+        uptr[(size_t)i] = nz + lower;
+        for (int j = head; j < n; j = next[(size_t)j]) {
+            ijlu[(size_t)nz] = j;
+            level[(size_t)nz] = rowlev[(size_t)j];
+            ++nz;
+        }
+        ijlu[(size_t)i + 1] = nz;
+    }
+    return nz;
+}
+
+// c = a b for nb x nb blocks in fasp_blas_smat_mul's order: each entry summed left to right; nb = 6 (no unrolled form in
+// the reference) starts from 0.0 and accumulates, as its default branch does
+void block_mul(const double* a, const double* b, double* c, int nb)
+{
+    for (int i = 0; i < nb; ++i)
+        for (int j = 0; j < nb; ++j) {
+            double s = nb == 6 ? 0.0 + a[i * nb] * b[j] : a[i * nb] * b[j];
+            for (int k = 1; k < nb; ++k) s = s + a[i * nb + k] * b[k * nb + j];
+            c[i * nb + j] = s;
+        }
+}
+
+// fasp_smat_inv_nc3 (BlaSmallMatInv.c:67): cofactors over the determinant, the identity for a near-singular block
+void block_inv3(double* a)
+{
+    const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], a6 = a[6], a7 = a[7], a8 = a[8];
+    const double M0 = a4 * a8 - a5 * a7, M3 = a2 * a7 - a1 * a8, M6 = a1 * a5 - a2 * a4;
+    const double M1 = a5 * a6 - a3 * a8, M4 = a0 * a8 - a2 * a6, M7 = a2 * a3 - a0 * a5;
+    const double M2 = a3 * a7 - a4 * a6, M5 = a1 * a6 - a0 * a7, M8 = a0 * a4 - a1 * a3;
+    const double det = a0 * M0 + a3 * M3 + a6 * M6;
+    if (std::fabs(det) < fasp::SMALLREAL) {
+        std::printf("### WARNING: Matrix is nearly singular, det = %e! Ignore.\n", det);
+        for (int e = 0; e < 9; ++e) a[e] = e % 4 == 0 ? 1.0 : 0.0;
+        return;
+    }
+    const double det_inv = 1.0 / det;
+    a[0] = M0 * det_inv; a[1] = M3 * det_inv; a[2] = M6 * det_inv;
+    a[3] = M1 * det_inv; a[4] = M4 * det_inv; a[5] = M7 * det_inv;
+    a[6] = M2 * det_inv; a[7] = M5 * det_inv; a[8] = M8 * det_inv;
+}
+
+// Numeric pass (BlaILUSetupBSR.c:819): block IKJ elimination on the symbolic pattern.  Row k: A's blocks scattered onto
+// the pattern (zeros elsewhere); for each L block in storage order, L_kj = L_kj U_jj^-1, then U_ks -= L_kj U_js for every
+// U block of row j whose column row k holds; finally the diagonal block is inverted (nb = 1: 1 / d; nb = 3: the closed
+// form; otherwise the pivoted Gauss-Jordan).  Returns the status of the LAST pivoted inverse (the reference's loop
+// overwrites it), FASP_SUCCESS when there is none.
+int bsr_numeric(const dBSRmat* A, const int* ijlu, const int* uptr, double* luval)
+{
+    const int n = A->ROW, nb = A->nb, nb2 = nb * nb;
+    std::vector<int> pos((size_t)n, 0);
+    std::vector<double> mult((size_t)nb2), upd((size_t)nb2);
+    int status = FASP_SUCCESS;
+    for (int k = 0; k < n; ++k) {
+        for (int p = ijlu[k]; p < ijlu[k + 1]; ++p) {
+            pos[(size_t)ijlu[p]] = p;
+            std::fill(luval + (size_t)p * nb2, luval + (size_t)(p + 1) * nb2, 0.0);
+        }
+        std::fill(luval + (size_t)k * nb2, luval + (size_t)(k + 1) * nb2, 0.0);
+        pos[(size_t)k] = k;
+        for (int q = A->IA[k]; q < A->IA[k + 1]; ++q)
+            std::memcpy(luval + (size_t)pos[(size_t)A->JA[q]] * nb2, A->val + (size_t)q * nb2, sizeof(double) * nb2);
+        for (int p = ijlu[k]; p < uptr[k]; ++p) {
+            const int j = ijlu[p];
+            double* L = luval + (size_t)p * nb2;
+            block_mul(L, luval + (size_t)j * nb2, mult.data(), nb);
+            std::memcpy(L, mult.data(), sizeof(double) * nb2);
+            for (int s = uptr[j]; s < ijlu[j + 1]; ++s) {
+                const int at = pos[(size_t)ijlu[s]];
+                if (at == 0) continue;
+                block_mul(mult.data(), luval + (size_t)s * nb2, upd.data(), nb);
+                double* U = luval + (size_t)at * nb2;
+                for (int e = 0; e < nb2; ++e) U[e] -= upd[(size_t)e];
+            }
+        }
+        for (int p = ijlu[k]; p < ijlu[k + 1]; ++p) pos[(size_t)ijlu[p]] = 0;
+        pos[(size_t)k] = 0;
+        double* D = luval + (size_t)k * nb2;
+        if (nb == 1) D[0] = 1.0 / D[0];
+        else if (nb == 3) block_inv3(D);
+        else {
+            status = fasp::smat_invp(D, nb);
+            if (status < 0) std::printf("### WARNING: The matrix is nearly singular!\n");
+        }
+    }
+    return status;
+}
+
 const char* fact_message(int e)
 {
     switch (e) {
@@ -371,10 +516,60 @@ short fasp_ilu_dcsr_setup(dCSRmat* A, ILU_data* iludata, ILU_param* iluparam)
         std::printf("### ERROR: ILU needs more RAM %d! [%s]\n", iwk - iludata->nzlu, __func__);
         return ERROR_SOLVER_ILUSETUP;
     }
-    fasp::ilu_register_host(iludata);
+    fasp::ilu_register_host(iludata, 0);
     if (iluparam->print_level > PRINT_NONE)
         std::printf("%s setup costs %f seconds.\n", type == ILUt ? "ILUt" : type == ILUtp ? "ILUtp" : "ILUk", fasp::wall_seconds() - t0);
     return FASP_SUCCESS;
+}
+
+// BlaILUSetupBSR.c:55.  Every ILU_type gives ILUk(ILU_lfil) (ILUt / ILUtp parameters are not read).  The factor is MSR over
+// block rows: ijlu as for the scalar factor, luval[p * nb^2 ..] the nb x nb block of entry p (row-major), luval[i * nb^2 ..]
+// the INVERSE of the i-th diagonal block.  Failure: ERROR_SOLVER_ILUSETUP (the pattern needs more than (lfil + 2) NNZ
+// entries, or a pivoted block inverse failed on the last block row).
+short fasp_ilu_dbsr_setup(dBSRmat* A, ILU_data* iludata, ILU_param* iluparam)
+{
+    const double t0 = fasp::wall_seconds();
+    const int lfil = iluparam->ILU_lfil;
+    iludata->type = 0;
+    iludata->iperm = nullptr;
+    iludata->A = nullptr;
+    iludata->ilevL = iludata->jlevL = nullptr;
+    iludata->ilevU = iludata->jlevU = nullptr;
+    iludata->ijlu = nullptr; iludata->luval = nullptr; iludata->work = nullptr;
+    iludata->nzlu = 0; iludata->nwork = 0;
+    if (!A || !A->IA || !A->JA || !A->val || A->ROW <= 0 || A->ROW != A->COL || A->nb < 1 || A->nb > 7 || lfil < 0) {
+        std::printf("### ERROR: ILU setup needs a square BSR matrix with 1 <= nb <= 7 and lfil >= 0! [%s]\n", __func__);
+        return ERROR_SOLVER_ILUSETUP;
+    }
+    const int n = A->ROW, nb = A->nb, nb2 = nb * nb;
+    iludata->row = iludata->col = n;
+    iludata->nb = nb;
+    const long long iwk_ll = (long long)(lfil + 2) * A->NNZ;
+    const int iwk = (int)std::min<long long>(iwk_ll, 0x7fffffffLL);
+
+    std::vector<int> ijlu, uptr;
+    const int nzlu = bsr_symbolic(A, lfil, iwk, ijlu, uptr);
+    if (nzlu < 0) {
+        if (nzlu == -1) std::printf("### ERROR: More storage needed! [fasp_symbfactor]\n");
+        else std::printf("### ERROR: Missing diagonal block or repeated column in a block row! [fasp_symbfactor]\n");
+        std::printf("### ERROR: ILU setup failed (ierr=%d)! [%s]\n", nzlu == -1 ? 1 : 2, __func__);
+        return ERROR_SOLVER_ILUSETUP;
+    }
+    iludata->luval = (double*)fasp_mem_calloc((unsigned)nzlu * (unsigned)nb2, sizeof(double));
+    const int status = bsr_numeric(A, ijlu.data(), uptr.data(), iludata->luval);
+    if (status < 0) {
+        std::printf("### ERROR: ILU factorization failed! [%s]\n", __func__);
+        return ERROR_SOLVER_ILUSETUP;
+    }
+    iludata->nzlu = nzlu;
+    iludata->nwork = 20 * n * nb;
+    iludata->ijlu = (int*)fasp_mem_calloc((unsigned)nzlu, sizeof(int));
+    std::memcpy(iludata->ijlu, ijlu.data(), sizeof(int) * (size_t)nzlu);
+    iludata->work = (double*)fasp_mem_calloc((unsigned)iludata->nwork, sizeof(double));
+    fasp::ilu_register_host(iludata, nb);
+    if (iluparam->print_level > PRINT_NONE)
+        std::printf("BSR ILU(%d)-seq setup costs %f seconds.\n", lfil, fasp::wall_seconds() - t0);
+    return (short)status;
 }
 
 }  // extern "C"

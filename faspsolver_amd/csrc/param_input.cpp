@@ -624,3 +624,24 @@ extern "C" void fasp_fwrapper_dcsr_krylov_ilu_(int* n, int* nnz, int* ia, int* j
     dvector rhs{*n, b}, sol{*n, u};
     fasp_solver_dcsr_krylov_ilu(&mat, &rhs, &sol, &itsparam, &iluparam);
 }
+
+// SolWrapper.c:326: block ILUk(0)-preconditioned VFGMRES on the caller's BSR arrays (row-major blocks, storage_manner 0)
+extern "C" void fasp_fwrapper_dbsr_krylov_ilu_(int* n, int* nnz, int* nb, int* ia, int* ja, double* a, double* b, double* u,
+                                               double* tol, int* maxit, int* ptrlvl)
+{
+    ILU_param iluparam;
+    ITS_param itsparam;
+    fasp_param_ilu_init(&iluparam);
+    iluparam.ILU_lfil = 0;
+    iluparam.print_level = (short)*ptrlvl;
+    fasp_param_solver_init(&itsparam);
+    itsparam.itsolver_type = SOLVER_VFGMRES;
+    itsparam.tol = *tol;
+    itsparam.maxit = *maxit;
+    itsparam.print_level = (short)*ptrlvl;
+    dBSRmat mat;
+    mat.ROW = *n; mat.COL = *n; mat.NNZ = *nnz; mat.nb = *nb; mat.storage_manner = 0;
+    mat.IA = ia; mat.JA = ja; mat.val = a;
+    dvector rhs{*n * *nb, b}, sol{*n * *nb, u};
+    fasp_solver_dbsr_krylov_ilu(&mat, &rhs, &sol, &itsparam, &iluparam);
+}

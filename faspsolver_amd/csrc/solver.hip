@@ -1462,8 +1462,16 @@ int krylov_plugin_bsr(const char* fn, int which, dBSRmat* A, dvector* b, dvector
     K.mxv = [Mp](const double* x, double* y) { bsr_mxv(*Mp, x, y); };
     K.resid = [Mp](const double* x, const double* bb, double* r) { bsr_resid(*Mp, x, bb, r); };
     std::unique_ptr<TmpVec> ddiag;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
+    int ilu_st = FASP_SUCCESS;
+    IluDev* ilu = h ? nullptr : ilu_of_precond_bsr(pc, n, ilu_tmp, &ilu_st);
+    if (ilu_st < 0) return ilu_st;
     if (h) {
         K.pc = [h](double* in, double** out) { return precond_amg_bsr(h, in, out); };
+    } else if (ilu) {
+        // the reference's block ILU preconditioner (PreBSR.c:347): recognised by its function pointer, both block
+        // triangular solves on the device
+        K.pc = [ilu](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, 0, in, ilu->z); };
     } else if (pc && pc->fct == fasp_precond_dbsr_diag && pc->data &&
                static_cast<precond_diag_bsr*>(pc->data)->diag.row == A->ROW * A->nb * A->nb) {
         // block-diagonal preconditioner of the reference (PreBSR.c:49): z_i = Dinv_i r_i on the device
@@ -1501,6 +1509,7 @@ int krylov_plugin_bsr(const char* fn, int which, dBSRmat* A, dvector* b, dvector
         st = gmres_device(K, db.d, du.d, which == 2 ? 1 : which == 4 ? 3 : 0, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
     }
     du.get(u->val);
+    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
     for (double* q : ws) if (q) (void)hipFree(q);
     if (hh) (void)hipFree(hh);
     return st;

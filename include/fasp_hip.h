@@ -669,7 +669,12 @@ void fasp_smoother_dcsr_L1diag(dvector* u, const int i_1, const int i_n, const i
  * ILU_data is uploaded for each call.  Without a device they refuse to run (no CPU fallback).
  * fasp_solver_dcsr_krylov_ilu(_M): setup (of A, or of M) + fasp_solver_dcsr_itsolver with that preconditioner, every
  * itsolver_type; the preconditioner stays in HBM.  fasp_smoother_dcsr_ilu (ItrSmootherCSR.c:1280): x += (LU)^-1 (b - A x).
- * ILU as an AMG smoother (ILU_levels > 0), block / structured ILU and Schwarz stay out of scope. */
+ * Block ILU (BlaILUSetupBSR.c:55, PreBSR.c:347, SolBSR.c:286, ItrSmootherBSR.c:1479): fasp_ilu_dbsr_setup is block ILUk
+ * (ILU_lfil; every ILU_type) on the HOST, equal to the reference's bytes (luval holds nb x nb blocks, the diagonal ones
+ * inverted), 1 <= nb <= 7; it needs no GPU.  fasp_precond_dbsr_ilu applies it with block triangular solves on the device
+ * (bit for bit the reference's z; resident from the first application until fasp_ilu_data_free, as above), the block
+ * Krylov methods recognise it and keep it in HBM; fasp_solver_dbsr_krylov_ilu = setup + fasp_solver_dbsr_itsolver.
+ * ILU as an AMG smoother (ILU_levels > 0), structured ILU and Schwarz stay out of scope. */
 void  fasp_param_ilu_init(ILU_param* iluparam);                                     /* AuxParam.c:595 */
 void  fasp_ilu_data_create(const int iwk, const int nwork, ILU_data* iludata);      /* PreDataInit.c:411 */
 void  fasp_ilu_data_free(ILU_data* iludata);                                        /* PreDataInit.c:445 */
@@ -684,6 +689,13 @@ int   fasp_solver_dcsr_krylov_ilu_M(dCSRmat* A, dvector* b, dvector* x, ITS_para
 void  fasp_smoother_dcsr_ilu(dCSRmat* A, dvector* b, dvector* x, void* data);
 /* SolWrapper.c:195: ILUk(2)-preconditioned VFGMRES on a caller's CSR arrays (Fortran calling convention) */
 void  fasp_fwrapper_dcsr_krylov_ilu_(int* n, int* nnz, int* ia, int* ja, double* a, double* b, double* u,
+                                     double* tol, int* maxit, int* ptrlvl);
+short fasp_ilu_dbsr_setup(dBSRmat* A, ILU_data* iludata, ILU_param* iluparam);      /* BlaILUSetupBSR.c:55 */
+void  fasp_precond_dbsr_ilu(double* r, double* z, void* data);                      /* PreBSR.c:347 */
+int   fasp_solver_dbsr_krylov_ilu(dBSRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam);
+void  fasp_smoother_dbsr_ilu(dBSRmat* A, dvector* b, dvector* x, void* data);       /* ItrSmootherBSR.c:1479 */
+/* SolWrapper.c:326: ILUk(0)-preconditioned VFGMRES on a caller's BSR arrays (Fortran calling convention) */
+void  fasp_fwrapper_dbsr_krylov_ilu_(int* n, int* nnz, int* nb, int* ia, int* ja, double* a, double* b, double* u,
                                      double* tol, int* maxit, int* ptrlvl);
 
 /* The AMG preconditioner as a `precond` -- the role of fasp_precond_setup(PREC_AMG, ..)

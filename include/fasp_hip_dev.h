@@ -45,7 +45,8 @@ int fasp_hip_measure_ceilings(double* out, size_t bytes, int reps);
  * is alive (uploaded at the first application, released by fasp_ilu_data_free).  fasp_hip_ilu_time: microseconds per solve
  * of one triangle (which: 1 = L, 2 = U) on the device copy, averaged over `reps` back-to-back solves after one warm-up; info
  * (may be NULL, 6 doubles) = {dependency levels, form (1 single launch, 0 level launches), bytes moved per solve, slab
- * entries (padded), entries, longest row}; < 0: error. */
+ * entries (padded), entries, longest row}; < 0: error.  A factor of fasp_ilu_dbsr_setup is timed as the block factor it
+ * is (the registry's record), its bytes counted from the block layout. */
 int    fasp_hip_ilu_resident_count(void);
 double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
 
