@@ -30,7 +30,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_solver_dbsr_pcg", "fasp_solver_dbsr_pbcgs", "fasp_solver_dbsr_pgmres", "fasp_solver_dbsr_pvgmres",
     "fasp_solver_dbsr_pvfgmres", "fasp_hip_bsr_precond_setup", "fasp_hip_bsr_precond_fct", "fasp_hip_bsr_precond_free",
     "fasp_hip_param_input", "fasp_fwrapper_dcsr_krylov_amg_", "fasp_dcsrvec_read2", "fasp_dvec_read",
-    "fasp_dbsr_read", "fasp_dcoo_read", "fasp_dcoo_read1", "fasp_dcoo_shift_read", "fasp_dmtx_read", "fasp_dmtxsym_read", "fasp_dvec_write", "fasp_dcsr_write_coo", "fasp_dcsrvec_write2", "fasp_fwrapper_dcsr_amg_", "fasp_fwrapper_dbsr_krylov_amg_", "fasp_hip_free_bsr", "fasp_hip_comm_selftest", "fasp_hip_amg_kernel_info", "fasp_hip_coding_selftest", "fasp_solver_amg", "fasp_solver_famg", "fasp_hip_amg_solve", "fasp_precond_diag", "fasp_precond_dbsr_diag", "fasp_solver_dcsr_itsolver", "fasp_solver_dcsr_krylov", "fasp_solver_dcsr_krylov_diag", "fasp_solver_dbsr_itsolver", "fasp_solver_dbsr_krylov", "fasp_solver_dbsr_krylov_diag", "fasp_hip_mxv_csr", "fasp_hip_mxv_bsr", "fasp_solver_matfree_init", "fasp_solver_pcg", "fasp_solver_pbcgs", "fasp_solver_pgcg", "fasp_solver_pminres", "fasp_solver_pgmres", "fasp_solver_pvgmres", "fasp_solver_pvfgmres", "fasp_solver_itsolver", "fasp_solver_krylov", "fasp_solver_dcsr_pcg", "fasp_solver_dcsr_pminres", "fasp_solver_dcsr_pgcg", "fasp_solver_dcsr_pgcr", "fasp_solver_dcsr_pbcgs", "fasp_solver_dcsr_pgmres", "fasp_solver_dcsr_pvgmres",
+    "fasp_dbsr_read", "fasp_dcoo_read", "fasp_dcoo_read1", "fasp_dcoo_shift_read", "fasp_dmtx_read", "fasp_dmtxsym_read", "fasp_dvec_write", "fasp_dcsr_write_coo", "fasp_dcsrvec_write2", "fasp_fwrapper_dcsr_amg_", "fasp_fwrapper_dbsr_krylov_amg_", "fasp_hip_free_bsr", "fasp_hip_comm_selftest", "fasp_hip_amg_kernel_info", "fasp_hip_coarse_kernel_info", "fasp_hip_bsr_coarse_kernel_info", "fasp_hip_coding_selftest", "fasp_solver_amg", "fasp_solver_famg", "fasp_hip_amg_solve", "fasp_precond_diag", "fasp_precond_dbsr_diag", "fasp_solver_dcsr_itsolver", "fasp_solver_dcsr_krylov", "fasp_solver_dcsr_krylov_diag", "fasp_solver_dbsr_itsolver", "fasp_solver_dbsr_krylov", "fasp_solver_dbsr_krylov_diag", "fasp_hip_mxv_csr", "fasp_hip_mxv_bsr", "fasp_solver_matfree_init", "fasp_solver_pcg", "fasp_solver_pbcgs", "fasp_solver_pgcg", "fasp_solver_pminres", "fasp_solver_pgmres", "fasp_solver_pvgmres", "fasp_solver_pvfgmres", "fasp_solver_itsolver", "fasp_solver_krylov", "fasp_solver_dcsr_pcg", "fasp_solver_dcsr_pminres", "fasp_solver_dcsr_pgcg", "fasp_solver_dcsr_pgcr", "fasp_solver_dcsr_pbcgs", "fasp_solver_dcsr_pgmres", "fasp_solver_dcsr_pvgmres",
     "fasp_solver_dcsr_pvfgmres", "fasp_hip_precond_setup", "fasp_hip_precond_fct", "fasp_hip_precond_free",
     "fasp_hip_time_bsr_mxv", "fasp_solver_dbsr_krylov_amg", "fasp_hip_bsr_amg_create", "fasp_hip_bsr_amg_create_host",
     "fasp_hip_bsr_amg_destroy", "fasp_hip_bsr_amg_num_levels", "fasp_hip_bsr_amg_get_matrix",
@@ -153,6 +153,8 @@ def lib():
     L.fasp_fwrapper_dcsr_krylov_amg_.restype = None
     L.fasp_hip_coding_selftest.argtypes = [P(T.dCSRmat), P(C.c_int)]
     L.fasp_hip_amg_kernel_info.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_int), P(C.c_double)]
+    L.fasp_hip_coarse_kernel_info.argtypes = [C.c_void_p, P(C.c_int)]
+    L.fasp_hip_bsr_coarse_kernel_info.argtypes = [C.c_void_p, P(C.c_int)]
     L.fasp_solver_amg.argtypes = [P(T.dCSRmat), P(T.dvector), P(T.dvector), P(T.AMG_param)]
     L.fasp_hip_amg_solve.argtypes = [C.c_void_p, P(T.dvector), P(T.dvector), P(T.AMG_param), T.c_double_p,
                                      C.c_int, P(T.fasp_hip_stats)]
@@ -460,6 +462,14 @@ class AMG:
             raise IndexError((level, which))
         return k.value, b.value
 
+    def coarse_kernel_info(self):
+        """The last coarsest-level solve: (family, instantiation, auxiliary, CG status, net ran, net status, compute units of the
+        device, 0) -- fasp_hip_dev.h."""
+        info = (C.c_int * 8)()
+        if lib().fasp_hip_coarse_kernel_info(self.h, info) < 0:
+            raise RuntimeError("fasp_hip_coarse_kernel_info failed")
+        return tuple(info)
+
     def precond(self, r):
         r = np.ascontiguousarray(r, dtype=np.float64)
         z = np.zeros_like(r)
@@ -558,6 +568,20 @@ class BSRAMG:
         st = lib().fasp_hip_bsr_solve(self.h, C.byref(bv), C.byref(xv), C.byref(itparam), T.dp(hist),
                                       hist_cap, C.byref(stats))
         return st, x, hist[:max(min(stats.nhist, hist_cap), 0)].copy(), stats
+
+    def precond(self, r):
+        """z = B r: maxit cycles of the resident block hierarchy from a zero guess (fasp_hip_bsr_precond_fct)."""
+        r = np.ascontiguousarray(r, dtype=np.float64).copy()
+        z = np.zeros_like(r)
+        lib().fasp_hip_bsr_precond_fct(T.dp(r), T.dp(z), self.h)
+        return z
+
+    def coarse_kernel_info(self):
+        """The last coarsest-level solve: (family, LV, cache2, GMRES status, iterations, 0, compute units, 0) -- fasp_hip_dev.h."""
+        info = (C.c_int * 8)()
+        if lib().fasp_hip_bsr_coarse_kernel_info(self.h, info) < 0:
+            raise RuntimeError("fasp_hip_bsr_coarse_kernel_info failed")
+        return tuple(info)
 
     def dist_info(self):
         """Row partition of level 0 (one process per GPU): owned block rows [row0, row0 + nloc)."""

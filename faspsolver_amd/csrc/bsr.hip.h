@@ -83,6 +83,7 @@ struct fasp_hip_amg_bsr {
     double*              gm_hh = nullptr;
     double*              small_ws = nullptr;  // workspace of the single-workgroup coarse GMRES
     long long            coarse_iters = 0, vcycles = 0;
+    int                  coarse_kinfo[6] = {0, 0, 0, 0, 0, 0};   // the last coarse solve (fasp_hip_bsr_coarse_kernel_info)
 };
 
 namespace fasp_bsr {
@@ -280,11 +281,14 @@ ForwardSweep:
             if (small_out_fetch(o) < 0) return ERROR_MISC;
             st = o.status;
             h->coarse_iters += o.iters;
+            h->coarse_kinfo[0] = 8; h->coarse_kinfo[1] = (g_tune.small_lds && lds <= 140 * 1024) ? 1 : 0; h->coarse_kinfo[2] = a.cache2;
+            h->coarse_kinfo[3] = o.status; h->coarse_kinfo[4] = o.iters;
         } else {
             KOps K = bsr_ops(h, nl - 1, 1);
             PcgOut po{BIGREAL, BIGREAL, BIGREAL};
             st = gmres_device(K, Lc.b, Lc.x, 0, ctol, atol, cmaxit, 25, STOP_REL_RES, 0, nullptr, &po);
             if (st >= 0) h->coarse_iters += st;
+            h->coarse_kinfo[0] = 9; h->coarse_kinfo[1] = 0; h->coarse_kinfo[2] = 0; h->coarse_kinfo[3] = st; h->coarse_kinfo[4] = std::max(st, 0);
         }
         if (st < 0 && st != ERROR_SOLVER_MAXIT && st != ERROR_SOLVER_STAG && st != ERROR_SOLVER_SOLSTAG &&
             st != ERROR_SOLVER_TOLSMALL) return st;  // device failure, not a convergence verdict

@@ -154,6 +154,7 @@ static int coarse_spcg(fasp_hip_amg* h, DevLevel& D, double tol, int prtlvl)
             }
             a.img = h->reg_img;
             const bool ahead = g_tune.small_onewave >= 4;   // the direction goes out before the tests of the iteration (a wavefront more: the first one multiplies nothing)
+            h->coarse_kinfo[0] = 1; h->coarse_kinfo[1] = NBK; h->coarse_kinfo[2] = ahead ? 1 : 0;
             if (NBK == 4 && ahead) hipLaunchKernelGGL((k_spcg_dpp<4, 4, true>), dim3(1), dim3(320), 0, g_ctx.stream, a, LD);
             else if (NBK == 4) hipLaunchKernelGGL((k_spcg_dpp<4, 4, false>), dim3(1), dim3(256), 0, g_ctx.stream, a, LD);
             else if (NBK == 6 && ahead) hipLaunchKernelGGL((k_spcg_dpp<6, 2, true>), dim3(1), dim3(256), 0, g_ctx.stream, a, LD);
@@ -185,6 +186,7 @@ static int coarse_spcg(fasp_hip_amg* h, DevLevel& D, double tol, int prtlvl)
                 attr_r = true;
             }
             const size_t lds_r = sizeof(double) * (2 * (size_t)MC + 4);
+            h->coarse_kinfo[0] = 2; h->coarse_kinfo[1] = MC; h->coarse_kinfo[2] = 0;
             if (m <= 64) hipLaunchKernelGGL(k_spcg_reg<32>, dim3(1), dim3(SPCG_REG_NT), lds_r, g_ctx.stream, a, LD);
             else if (m <= 96) hipLaunchKernelGGL(k_spcg_reg<48>, dim3(1), dim3(SPCG_REG_NT), lds_r, g_ctx.stream, a, LD);
             else hipLaunchKernelGGL(k_spcg_reg<64>, dim3(1), dim3(SPCG_REG_NT), lds_r, g_ctx.stream, a, LD);
@@ -193,13 +195,20 @@ static int coarse_spcg(fasp_hip_amg* h, DevLevel& D, double tol, int prtlvl)
             static bool attr_w = false;
             if (!attr_w) { (void)hipFuncSetAttribute((const void*)k_spcg_wave, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr_w = true; }
             hipLaunchKernelGGL(k_spcg_wave, dim3(1), dim3(64), lds_w, g_ctx.stream, a, LD);
+            h->coarse_kinfo[0] = 3; h->coarse_kinfo[1] = 0; h->coarse_kinfo[2] = 0;
         }
-        else if (g_tune.small_lds && lds_v + lds_m <= 148 * 1024)
+        else if (g_tune.small_lds && lds_v + lds_m <= 148 * 1024) {
             hipLaunchKernelGGL((k_spcg_small<true, true>), dim3(1), dim3(SMALL_BLOCK), lds_v + lds_m, g_ctx.stream, a);
-        else if (g_tune.small_lds && lds_v <= 148 * 1024)
+            h->coarse_kinfo[0] = 4; h->coarse_kinfo[1] = 2; h->coarse_kinfo[2] = 0;
+        }
+        else if (g_tune.small_lds && lds_v <= 148 * 1024) {
             hipLaunchKernelGGL((k_spcg_small<true, false>), dim3(1), dim3(SMALL_BLOCK), lds_v, g_ctx.stream, a);
-        else
+            h->coarse_kinfo[0] = 4; h->coarse_kinfo[1] = 1; h->coarse_kinfo[2] = 0;
+        }
+        else {
             hipLaunchKernelGGL((k_spcg_small<false, false>), dim3(1), dim3(SMALL_BLOCK), 0, g_ctx.stream, a);
+            h->coarse_kinfo[0] = 4; h->coarse_kinfo[1] = 0; h->coarse_kinfo[2] = 0;
+        }
         D.x_zero = false;
         if (a.lazy) return FASP_SUCCESS;   // the verdict is read once per application of the preconditioner (precond_amg)
         SmallOut o;
@@ -304,6 +313,7 @@ ITERATE:
                 else if (PP.NE == 56) lst = launch_spcg_persist<56>(pa, lds);
                 else lst = launch_spcg_persist<64>(pa, lds);
                 if (lst < 0) return lst;
+                h->coarse_kinfo[0] = 6; h->coarse_kinfo[1] = PP.NE; h->coarse_kinfo[2] = pa.u_lds;
             }
             for (int q = 0; q < batch && fused && !persist; ++q) {
                 SpcgFusedArgs fa{};
@@ -318,6 +328,7 @@ ITERATE:
                 if (m <= 512 * 4) hipLaunchKernelGGL(k_spcg_fused<4>, grid, dim3(512), lds, s, fa);
                 else if (m <= 512 * 10) hipLaunchKernelGGL(k_spcg_fused<10>, grid, dim3(512), lds, s, fa);
                 else hipLaunchKernelGGL(k_spcg_fused<16>, grid, dim3(512), lds, s, fa);
+                h->coarse_kinfo[0] = 5; h->coarse_kinfo[1] = m <= 512 * 4 ? 4 : m <= 512 * 10 ? 10 : 16; h->coarse_kinfo[2] = 0;
                 cur ^= 1; first = false;
             }
             for (int q = 0; q < batch && !fused; ++q) {
@@ -329,6 +340,7 @@ ITERATE:
                 if (m <= 512 * 4) hipLaunchKernelGGL(k_spcg_step_reg<4>, dim3(1), dim3(512), 0, s, sa);
                 else if (m <= 512 * 10) hipLaunchKernelGGL(k_spcg_step_reg<10>, dim3(1), dim3(512), 0, s, sa);
                 else hipLaunchKernelGGL(k_spcg_step, dim3(1), dim3(SMALL_BLOCK), 0, s, sa);
+                h->coarse_kinfo[0] = 7; h->coarse_kinfo[1] = m <= 512 * 4 ? 4 : m <= 512 * 10 ? 10 : 0; h->coarse_kinfo[2] = 0;
             }
             // The persistent kernel normally ends because the recurrence's residual met the tolerance, and the reference then forms the TRUE
             // residual (Check III, KrySPcg.c:258-275): a second wait of the host per coarse solve.  It is queued here, behind the kernel,

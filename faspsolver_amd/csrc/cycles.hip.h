@@ -10,6 +10,7 @@ static int coarse_solve(fasp_hip_amg* h, const AMG_param& param, double tol)
     const int nl = (int)h->L.size();
     DevLevel& Lc = h->L[nl - 1];
     int st = coarse_spcg(h, Lc, tol, param.print_level);
+    h->coarse_kinfo[3] = st; h->coarse_kinfo[4] = 0; h->coarse_kinfo[5] = 0;   // (a lazily read verdict shows as 0 here)
     if (st == ERROR_MISC) return st;  // device failure, not a solver verdict
     if (st < 0) {
         // safety net of PreMGUtil.inl:50-52: fasp_solver_dcsr_spvgmres(A, b, x, NULL, ctol, maxit, 20, 1, ..)
@@ -19,6 +20,7 @@ static int coarse_solve(fasp_hip_amg* h, const AMG_param& param, double tol)
         KOps Kc = csr_ops(h, nl - 1, false);
         st = gmres_device(Kc, Lc.b, Lc.x, 2, tol, 0.0, maxit, 20, STOP_REL_RES, param.print_level - 4,
                           nullptr, nullptr);
+        h->coarse_kinfo[4] = 1; h->coarse_kinfo[5] = st;
         if (st == ERROR_MISC) return st;
         if (st < 0 && param.print_level >= PRINT_MORE) {
             std::printf("### WARNING: Coarse level solver did not converge!\n");

@@ -105,6 +105,8 @@ struct fasp_hip_amg {
     std::vector<EventPair> ev;
     int                    ev_used = 0;
     long long              coarse_iters = 0, vcycles = 0;
+    // the last coarse solve (fasp_hip_coarse_kernel_info): {kernel family, instantiation, auxiliary, status of the safe CG, net ran, status of the net}
+    int                    coarse_kinfo[6] = {0, 0, 0, 0, 0, 0};
     // lazy coarse verdicts (precond_amg): device words {min status, iteration sum}, their pinned host copy; coarse_sync: a coarse
     // solve gave up once on this hierarchy -- verdicts are read per solve from then on
     int*                   d_lazy = nullptr; int* h_lazy = nullptr; bool lazy_active = false, coarse_sync = false;

@@ -591,6 +591,24 @@ int fasp_hip_amg_kernel_info(const fasp_hip_amg* h, int level, int which, int* k
     return FASP_SUCCESS;
 }
 
+int fasp_hip_coarse_kernel_info(const fasp_hip_amg* h, int* info)
+{
+    FASP_ENTRY();
+    if (!h || !info) return ERROR_INPUT_PAR;
+    for (int i = 0; i < 6; ++i) info[i] = h->coarse_kinfo[i];
+    info[6] = g_ctx.num_cu; info[7] = 0;
+    return FASP_SUCCESS;
+}
+
+int fasp_hip_bsr_coarse_kernel_info(const fasp_hip_amg_bsr* h, int* info)
+{
+    FASP_ENTRY();
+    if (!h || !info) return ERROR_INPUT_PAR;
+    for (int i = 0; i < 6; ++i) info[i] = h->coarse_kinfo[i];
+    info[6] = g_ctx.num_cu; info[7] = 0;
+    return FASP_SUCCESS;
+}
+
 int fasp_hip_amg_get_matrix(const fasp_hip_amg* h, int level, int which, dCSRmat* view)
 {
     FASP_ENTRY();

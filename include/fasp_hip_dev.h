@@ -86,6 +86,21 @@ double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
  *     read at upload).
  * Unknown keys return ERROR_INPUT_PAR. */
 int fasp_hip_tune(const char* key, int value);
+/* Which kernel served the last coarsest-level solve of a hierarchy, and how it ended (read-only; tests).  info (8 ints) =
+ *   [0] family: 0 none yet, 1 k_spcg_dpp, 2 k_spcg_reg, 3 k_spcg_wave, 4 k_spcg_small, 5 k_spcg_fused, 6 k_spcg_persist,
+ *       7 launch_csr<OP_MXV_DOT> + k_spcg_step_reg / k_spcg_step (the last family launched: a persistent kernel that gave
+ *       up waiting and handed over to the per-iteration kernels shows as those);
+ *   [1] instantiation: k_spcg_dpp NBK (4, 6, 8); k_spcg_reg MC (32, 48, 64); k_spcg_small 2 = matrix and vectors in LDS,
+ *       1 = vectors, 0 = nothing; k_spcg_fused 4 / 10 / 16; k_spcg_persist NE (32, 48, 56, 64); step kernels 4 / 10 =
+ *       k_spcg_step_reg, 0 = k_spcg_step;
+ *   [2] k_spcg_dpp: 1 = send-ahead form; k_spcg_persist: u_lds;
+ *   [3] what the safe CG returned (iterations, or its negative verdict); [4] 1 = the SPVGMRES net ran behind it; [5] its return value;
+ *   [6] compute units of the device (build_persist_plan deals the rows to ([6] - 1) * 8 wavefronts); [7] 0. */
+int fasp_hip_coarse_kernel_info(const fasp_hip_amg* h, int* info);
+/* The same for the coarsest level of a block hierarchy.  info (8 ints) = [0] family: 0 none yet, 8 k_gmres_small<SmallBSR, LV>,
+ * 9 the general device GMRES (gmres_device); [1] LV (the basis in LDS); [2] cache2 (nb = 3: the blocks of the rows beyond the first
+ * 512 in LDS); [3] what the GMRES returned; [4] its iterations; [5] 0; [6] compute units of the device; [7] 0. */
+int fasp_hip_bsr_coarse_kernel_info(const fasp_hip_amg_bsr* h, int* info);
 
 /* Counters of the communicator since the last reset: out[0] halo exchanges, [1] all-reduces, [2] all-gathers, [3] doubles sent in
  * exchanges, [4] doubles contributed to all-gathers, [5..7] seconds spent in the three -- filled only in the diagnostic mode

@@ -185,6 +185,8 @@ typedef struct {
 int  orc_amg_setup_ua_bsr(orc_amg_bsr* mgl, const dBSRmat* A, AMG_param* param);
 void orc_amg_bsr_free(orc_amg_bsr* mgl);
 void orc_mgcycle_bsr(orc_amg_bsr* mgl, const AMG_param* param);
+int  orc_gmres_bsr(int mode, const dBSRmat* A, const dvector* b, dvector* x, double tol, double abstol, int MaxIt, int restart,
+                   int StopType, int PrtLvl, double* final_relres);
 int  orc_solver_dbsr_krylov_amg(dBSRmat* A, dvector* b, dvector* x, ITS_param* itparam,
                                 AMG_param* amgparam, int* num_levels, double* final_relres);
 int  orc_sizeof_amg_bsr(void);
