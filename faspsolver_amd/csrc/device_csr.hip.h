@@ -52,8 +52,20 @@ struct DevCSR {
     unsigned short* es_ja16 = nullptr;   // 16-bit columns relative to the chunk's smallest column (operators with > 65536 columns)
     double*    es_part = nullptr;   // 2 W doubles + W counters behind them
     int        es_W = 0, es_nc = 0;
+    // k_csr_sell (kernels4.hip.h): value-indexed sliced-ELL form of a mid-length-row operator with few distinct values (build_sell)
+    unsigned*      sell_code = nullptr;   // one 32-bit word per slot
+    int*           sell_meta = nullptr;   // one allocation: sptr[nslice + 1], sbase[nslice]
+    unsigned char* sell_rlen = nullptr;
+    double*        sell_tab = nullptr;
+    int            sell_nv = 0, sell_obits = 0, sell_nslice = 0;
+    long long      sell_slots = 0;
     void    release()
     {
+        if (sell_code) (void)hipFree(sell_code);
+        if (sell_meta) (void)hipFree(sell_meta);
+        if (sell_rlen) (void)hipFree(sell_rlen);
+        if (sell_tab) (void)hipFree(sell_tab);
+        sell_code = nullptr; sell_meta = nullptr; sell_rlen = nullptr; sell_tab = nullptr; sell_nv = sell_obits = sell_nslice = 0; sell_slots = 0;
         if (es_tab) (void)hipFree(es_tab);
         if (es_part) (void)hipFree(es_part);
         if (es_ja16) (void)hipFree(es_ja16);
@@ -724,6 +736,224 @@ static int estream_selftest_host(const int* ia, int nrow, int nnz, int per_wave,
     return 0;
 }
 
+// Value-indexed sliced-ELL coding (kernels4.hip.h, k_csr_sell) of an operator in the row-length range of k_csr_wstream2 /
+// k_csr_xtile.  Slices of 64 consecutive rows in the operator's own numbering; per slice its smallest column and its longest
+// row; per row its length; per entry one 32-bit word = index into the table of the distinct values (compared by bit pattern;
+// ordered by frequency, ties by bit pattern: deterministic) << obits | column - the slice's smallest column.  A row's entries
+// keep their storage order and are padded at the end, to the slice's longest row, with the word 0.  Lossless.
+// Qualifies only if (why_not, when it does not): 1 the operator is outside the size / mean-row-length range; 2 a row has
+// more than 255 entries; 3 slots > cap_percent / 100 x entries; 4 more than SELL_MAXV distinct values; 5 index and offset
+// do not fit 32 bits together.
+struct SellHost {
+    int nslice = 0, nv = 0, vbits = 0, obits = 0;
+    long long slots = 0;
+    std::vector<int> sptr, sbase;
+    std::vector<unsigned char> rlen;
+    std::vector<double> tab;
+    Buf<unsigned> code;
+    double bytes(int nrow) const { return 4.0 * (double)slots + (double)nrow + 4.0 * (2.0 * nslice + 1.0) + 8.0 * nv; }
+};
+constexpr int SELL_CAP_PERCENT = 125;
+static bool build_sell(const HostCSR& M, SellHost& S, int cap_percent, int* why_not)
+{
+    int dummy = 0;
+    int& why = why_not ? *why_not : dummy;
+    why = 1;
+    const int n = M.row;
+    if (n <= 0 || M.nnz < 4096 || (double)M.nnz > 48.0 * n || (double)M.nnz <= 7.6 * n) return false;   // (shorter rows: k_csr_lstream)
+    if ((long long)M.col >= (1ll << 28)) return false;
+    const int ns = (n + 63) / 64;
+    // row lengths, slice widths
+    S.rlen.assign((size_t)n, 0);
+    S.sptr.assign((size_t)ns + 1, 0);
+    int toolong = 0;
+#pragma omp parallel for schedule(static) reduction(+ : toolong)
+    for (int s = 0; s < ns; ++s) {
+        int W = 0;
+        for (int r = s * 64; r < std::min(n, s * 64 + 64); ++r) {
+            const int len = M.ia[r + 1] - M.ia[r];
+            if (len > 255) { ++toolong; continue; }
+            S.rlen[(size_t)r] = (unsigned char)len;
+            W = std::max(W, len);
+        }
+        S.sptr[(size_t)s + 1] = W;
+    }
+    if (toolong) { why = 2; return false; }
+    long long wsum = 0;
+    for (int s = 0; s < ns; ++s) wsum += S.sptr[(size_t)s + 1];
+    S.nslice = ns;
+    S.slots = 64ll * wsum;
+    if (S.slots * 100 > (long long)cap_percent * M.nnz || wsum >= (1ll << 30)) { why = 3; return false; }
+    for (int s = 0; s < ns; ++s) S.sptr[(size_t)s + 1] += S.sptr[(size_t)s];
+    // distinct values: per-thread sets with counts (a thread gives up beyond the cap), merged
+    constexpr int VSLOTS = 32768;
+    struct VSet {
+        std::vector<unsigned long long> key;
+        std::vector<long long> cnt;   // 0: empty slot
+        std::vector<int> id;          // index in the table (set once the order is known)
+        int n = 0;
+        VSet() : key((size_t)VSLOTS, 0ull), cnt((size_t)VSLOTS, 0), id((size_t)VSLOTS, -1) {}
+        static unsigned slot_of(unsigned long long b) { return (unsigned)((b * 0x9E3779B97F4A7C15ull) >> 49); }
+        bool add(unsigned long long b, long long c)
+        {
+            unsigned s = slot_of(b);
+            for (;;) {
+                if (cnt[s] == 0) {
+                    if (n >= SELL_MAXV) return false;
+                    key[s] = b; cnt[s] = c; ++n;
+                    return true;
+                }
+                if (key[s] == b) { cnt[s] += c; return true; }
+                s = (s + 1) & (VSLOTS - 1);
+            }
+        }
+        int slot(unsigned long long b) const   // -1: not in the set
+        {
+            unsigned s = slot_of(b);
+            for (;;) {
+                if (cnt[s] == 0) return -1;
+                if (key[s] == b) return (int)s;
+                s = (s + 1) & (VSLOTS - 1);
+            }
+        }
+    };
+    auto bits_of = [](double v) { unsigned long long b; std::memcpy(&b, &v, 8); return b; };
+    const int nt = std::max(1, std::min(omp_get_max_threads(), n / 4096 + 1));
+    std::vector<VSet*> local((size_t)nt, nullptr);
+    bool fail = false;
+#pragma omp parallel num_threads(nt)
+    {
+        VSet* T = new VSet();
+        local[(size_t)omp_get_thread_num()] = T;
+#pragma omp for schedule(static)
+        for (int r = 0; r < n; ++r) {
+            if (fail) continue;
+            for (int k = M.ia[r]; k < M.ia[r + 1]; ++k)
+                if (!T->add(bits_of(M.val[k]), 1)) { fail = true; break; }
+        }
+    }
+    VSet Gs;
+    for (VSet* T : local) {
+        if (T && !fail)
+            for (int s = 0; s < VSLOTS && !fail; ++s)
+                if (T->cnt[(size_t)s] && !Gs.add(T->key[(size_t)s], T->cnt[(size_t)s])) fail = true;
+        delete T;
+    }
+    if (fail) { why = 4; return false; }
+    std::vector<std::pair<long long, unsigned long long>> order;   // (-count, bits)
+    for (int s = 0; s < VSLOTS; ++s)
+        if (Gs.cnt[(size_t)s]) order.emplace_back(-Gs.cnt[(size_t)s], Gs.key[(size_t)s]);
+    std::sort(order.begin(), order.end());
+    S.nv = (int)order.size();
+    S.tab.resize(order.size());
+    for (size_t i = 0; i < order.size(); ++i) std::memcpy(&S.tab[i], &order[i].second, 8);
+    for (size_t i = 0; i < order.size(); ++i) Gs.id[(size_t)Gs.slot(order[i].second)] = (int)i;
+    S.vbits = 0;
+    while ((1ll << S.vbits) < S.nv) ++S.vbits;
+    // slice bases, widest offset
+    S.sbase.assign((size_t)ns, 0);
+    int maxoff = 0;
+#pragma omp parallel for schedule(static) reduction(max : maxoff)
+    for (int s = 0; s < ns; ++s) {
+        const int k0 = M.ia[s * 64], k1 = M.ia[std::min(n, s * 64 + 64)];
+        if (k1 <= k0) continue;
+        int lo = M.ja[k0], hi = lo;
+        for (int k = k0 + 1; k < k1; ++k) { lo = std::min(lo, M.ja[k]); hi = std::max(hi, M.ja[k]); }
+        S.sbase[(size_t)s] = lo;
+        maxoff = std::max(maxoff, hi - lo);
+    }
+    S.obits = 1;
+    while ((1ll << S.obits) <= maxoff) ++S.obits;
+    if (S.vbits + S.obits > 32) { why = 5; return false; }
+    // the words
+    S.code.alloc((size_t)std::max<long long>(S.slots, 1));
+    bool lost = false;
+#pragma omp parallel for schedule(static)
+    for (int s = 0; s < ns; ++s) {
+        const int W = S.sptr[(size_t)s + 1] - S.sptr[(size_t)s], base = S.sbase[(size_t)s];
+        unsigned* cs = S.code.data() + (size_t)S.sptr[(size_t)s] * 64;
+        for (int l = 0; l < 64; ++l) {
+            const int r = s * 64 + l;
+            const int kb = r < n ? M.ia[r] : 0, len = r < n ? M.ia[r + 1] - kb : 0;
+            for (int k = 0; k < len; ++k) {
+                const int sl = Gs.slot(bits_of(M.val[kb + k]));
+                if (sl < 0) { lost = true; continue; }
+                const int id = Gs.id[(size_t)sl];
+                cs[(size_t)k * 64 + l] = ((unsigned)id << S.obits) | (unsigned)(M.ja[kb + k] - base);
+            }
+            for (int k = len; k < W; ++k) cs[(size_t)k * 64 + l] = 0u;
+        }
+    }
+    if (lost) { why = 4; return false; }
+    why = 0;
+    return true;
+}
+
+// y = A x over the coded form, walked the way k_csr_sell walks it: slice by slice, a lane per row, step k of all rows of the slice before
+// step k + 1, every row summed left to right from 0.0
+static void sell_mxv_host(const SellHost& S, int nrow, const double* x, double* y)
+{
+    const unsigned omask = (1u << S.obits) - 1u;
+    for (int s = 0; s < S.nslice; ++s) {
+        const int W = S.sptr[(size_t)s + 1] - S.sptr[(size_t)s], base = S.sbase[(size_t)s];
+        const unsigned* cs = S.code.data() + (size_t)S.sptr[(size_t)s] * 64;
+        double acc[64];
+        for (int l = 0; l < 64; ++l) acc[l] = 0.0;
+        for (int k = 0; k < W; ++k)
+            for (int l = 0; l < 64; ++l) {
+                const int r = s * 64 + l;
+                if (r >= nrow || k >= (int)S.rlen[(size_t)r]) continue;
+                const unsigned c = cs[(size_t)k * 64 + l];
+                acc[l] = acc[l] + S.tab[c >> S.obits] * x[base + (int)(c & omask)];
+            }
+        for (int l = 0; l < 64 && s * 64 + l < nrow; ++l) y[s * 64 + l] = acc[l];
+    }
+}
+// the coded form back to CSR (ia: nrow + 1; ja, val: as many entries as the row lengths add up to)
+static void sell_decode_host(const SellHost& S, int nrow, int* ia, int* ja, double* val)
+{
+    const unsigned omask = (1u << S.obits) - 1u;
+    ia[0] = 0;
+    for (int r = 0; r < nrow; ++r) ia[r + 1] = ia[r] + (int)S.rlen[(size_t)r];
+    for (int r = 0; r < nrow; ++r) {
+        const int s = r >> 6, l = r & 63, base = S.sbase[(size_t)s];
+        const unsigned* cs = S.code.data() + (size_t)S.sptr[(size_t)s] * 64;
+        for (int k = 0; k < (int)S.rlen[(size_t)r]; ++k) {
+            const unsigned c = cs[(size_t)k * 64 + l];
+            ja[ia[r] + k] = base + (int)(c & omask);
+            val[ia[r] + k] = S.tab[c >> S.obits];
+        }
+    }
+}
+
+static int upload_sell(const HostCSR& H, DevCSR& D)
+{
+    static const bool on = !(std::getenv("FASP_HIP_SELL") && std::atoi(std::getenv("FASP_HIP_SELL")) == 0);
+    if (!on) return FASP_SUCCESS;
+    static const bool timing = std::getenv("FASP_HIP_SETUP_TIMING") != nullptr;
+    const double t0 = wall_seconds();
+    SellHost S;
+    int why = 0;
+    const bool ok = build_sell(H, S, SELL_CAP_PERCENT, &why);
+    if (timing) std::printf("        [sell %d x %d, %d nnz] %s (%d) %d values, %d + %d bits, %.3f slots per entry, %.3f s\n", H.row, H.col, H.nnz,
+                            ok ? "coded" : "not coded", why, S.nv, S.vbits, S.obits, (double)S.slots / std::max(H.nnz, 1), wall_seconds() - t0);
+    if (!ok) return FASP_SUCCESS;
+    const size_t ns = (size_t)S.nslice;
+    std::vector<int> meta(2 * ns + 1);
+    std::copy(S.sptr.begin(), S.sptr.end(), meta.begin());
+    std::copy(S.sbase.begin(), S.sbase.end(), meta.begin() + (long)ns + 1);
+    HIPCK(hipMalloc(&D.sell_code, sizeof(unsigned) * (size_t)std::max<long long>(S.slots, 1)));
+    HIPCK(hipMalloc(&D.sell_meta, sizeof(int) * meta.size()));
+    HIPCK(hipMalloc(&D.sell_rlen, (size_t)H.row));
+    HIPCK(hipMalloc(&D.sell_tab, sizeof(double) * (size_t)S.nv));
+    HIPCK(hipMemcpy(D.sell_code, S.code.data(), sizeof(unsigned) * (size_t)S.slots, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(D.sell_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(D.sell_rlen, S.rlen.data(), (size_t)H.row, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(D.sell_tab, S.tab.data(), sizeof(double) * (size_t)S.nv, hipMemcpyHostToDevice));
+    D.sell_nv = S.nv; D.sell_obits = S.obits; D.sell_nslice = S.nslice; D.sell_slots = S.slots;
+    return FASP_SUCCESS;
+}
+
 static int upload_csr(const HostCSR& H, DevCSR& D)
 {
     D.row = H.row; D.col = H.col; D.nnz = H.nnz;
@@ -873,12 +1103,14 @@ static int upload_csr(const HostCSR& H, DevCSR& D)
     }
     if (upload_plain() < 0) return ERROR_ALLOC_MEM;
     if (D.kind == 2 && !g_oneshot_upload && build_xtile(H, D) < 0) return ERROR_ALLOC_MEM;
+    // neither row patterns nor a byte dictionary: the value-indexed sliced-ELL form where the operator has few distinct values
+    if (D.kind == 2 && compress_enabled() && upload_sell(H, D) < 0) return ERROR_ALLOC_MEM;
     if (upload_ja16(D, H.ia.data(), H.ja.data()) < 0) return ERROR_ALLOC_MEM;
     return build_estream(H.ia.data(), H.row, H.nnz, D);
 }
 
 // development knobs (fasp_hip_tune): -1 = automatic
-struct Tuning { int gen2 = 2, ws2_bpc = 3, maxgrid = -1, xcd = 16, nt = 1, kind = -1, lanes = -1, wrows = -1, wcap = -1, compress = 1, rpl = -1, lds_tab = 1, xcd_pat = 64, spcg_batch = 16, small_lds = 1, ja16 = 1, spcg_fused = 1, spcg_grid = 0, spcg_persist = 1, split_rows = 0, gs_multicolor = 0, seq_flow = 1, seq_strip_kb = 0, seq_jobs = 1, seq_spine = 1, seq_grid = 0, seq_chain = 1, seq_chain_n1 = 0, seq_chain_grid = 0, seq_chain_ref = 0, seq_test_hang = 0, seq_rest_lanes = 0, local_square = 1, fuse_zr = 1, fuse_presmooth = 1, seq_lanes = 0, xtile = 1, rp5_max = 45, rp_bpc = 5, rp_xcd = -1, rp_strip = 2, spcg_test_hang = 0, small_onewave = 4, lazy_coarse = 1, rp_stream = -1, renumber = 1, renumber_chunk = 262144, pcg_dev_beta = 1, spcg_spec = 1, ev_every = 4, pcg_fold = 1, seq_chain_touch = 8, seq_chain_touch_t1 = 1, seq_zero_skip = 1, estream = 1, es_dbg = 0, ilu_form = -1; };
+struct Tuning { int gen2 = 2, ws2_bpc = 3, maxgrid = -1, xcd = 16, nt = 1, kind = -1, lanes = -1, wrows = -1, wcap = -1, compress = 1, rpl = -1, lds_tab = 1, xcd_pat = 64, spcg_batch = 16, small_lds = 1, ja16 = 1, spcg_fused = 1, spcg_grid = 0, spcg_persist = 1, split_rows = 0, gs_multicolor = 0, seq_flow = 1, seq_strip_kb = 0, seq_jobs = 1, seq_spine = 1, seq_grid = 0, seq_chain = 1, seq_chain_n1 = 0, seq_chain_grid = 0, seq_chain_ref = 0, seq_test_hang = 0, seq_rest_lanes = 0, local_square = 1, fuse_zr = 1, fuse_presmooth = 1, seq_lanes = 0, xtile = 1, rp5_max = 45, rp_bpc = 5, rp_xcd = -1, rp_strip = 2, spcg_test_hang = 0, small_onewave = 4, lazy_coarse = 1, rp_stream = -1, renumber = 1, renumber_chunk = 262144, pcg_dev_beta = 1, spcg_spec = 1, ev_every = 4, pcg_fold = 1, seq_chain_touch = 8, seq_chain_touch_t1 = 1, seq_zero_skip = 1, estream = 1, es_dbg = 0, ilu_form = -1, sell = 1; };
 static Tuning g_tune;
 
 // Blocks of one kernel instantiation that are co-resident on a CU (VGPR / LDS / wave
@@ -910,6 +1142,38 @@ static int launch_persistent(K kernel, int ntiles, CsrArgs& a, int blocks_per_cu
     int grid = std::min(cap, ntiles);
     grid = std::max(8, (grid + 7) / 8 * 8);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), 0, g_ctx.stream, a);
+    return grid;
+}
+
+// k_csr_sell (kernels4.hip.h): workgroups of 16 waves with the value table in dynamic LDS, grid = what is resident
+// (an operator that also has k_csr_xtile's lists keeps that kernel: it was selected there by measurement)
+static bool sell_active(const DevCSR& M) { return M.sell_code && g_tune.compress && g_tune.sell && g_tune.gen2 >= 2 && !(g_tune.xtile && M.lja16); }
+template <int OP>
+static int launch_sell(const DevCSR& M, CsrArgs& a)
+{
+    a.sell_code = M.sell_code; a.sell_sptr = M.sell_meta; a.sell_sbase = M.sell_meta + M.sell_nslice + 1; a.sell_rlen = M.sell_rlen;
+    a.sell_tab = M.sell_tab; a.sell_nv = M.sell_nv; a.sell_obits = M.sell_obits;
+    const size_t lds = sizeof(double) * ((size_t)M.sell_nv + SELL_NW);
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_csr_sell<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * (SELL_MAXV + SELL_NW)));
+        attr_set = true;
+    }
+    static std::vector<std::pair<size_t, int>> cache;   // resident workgroups per CU by table size
+    int nb = 0;
+    for (const auto& e : cache)
+        if (e.first == lds) nb = e.second;
+    if (nb == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_csr_sell<OP>, SELL_BLOCK, lds) != hipSuccess || nb < 1) nb = 1;
+        nb = std::min(nb, 2);
+        cache.emplace_back(lds, nb);
+    }
+    int cap = nb * g_ctx.num_cu;
+    if (g_tune.maxgrid > 0) cap = g_tune.maxgrid;
+    cap = std::min(cap, MAXGRID);
+    int grid = std::min(cap, a.ntiles);
+    grid = std::max(8, (grid + 7) / 8 * 8);
+    hipLaunchKernelGGL(k_csr_sell<OP>, dim3(grid), dim3(SELL_BLOCK), lds, g_ctx.stream, a);
     return grid;
 }
 
@@ -1088,6 +1352,13 @@ static int launch_csr(const DevCSR& M0, CsrArgs a, RowWin win = RowWin())
         a.lja16 = M.lja16; a.tptr = M.tptr; a.tcols = M.tcols;
         if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
         return launch_persistent(k_csr_xtile<OP>, a.ntiles, a, 3);
+    }
+    if (M.kind == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512 && (OP != OP_JACOBI || (M.dpos && !M.dup_diag))) {
+        // mid-length rows, few distinct values, tiles that share too few columns for k_csr_xtile: sliced ELL, lane = row, 4 bytes per entry
+        // (the rows' sums are k_csr_wstream2's)
+        set_tiles(SELL_BLOCK);
+        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
+        return launch_sell<OP>(M, a);
     }
     if (M.kind == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512 && (OP != OP_JACOBI || (M.dpos && !M.dup_diag)))
     {

@@ -97,6 +97,13 @@ struct CsrArgs {
     const unsigned short* es_ja16;   // 16-bit columns relative to es_cbase (nullptr: ja16 as it is)
     double*       es_part;    // 2 per wave: head part, tail part
     unsigned*     es_cnt;     // per wave: parts arrived (zero between launches)
+    // k_csr_sell (kernels4.hip.h): value-indexed sliced-ELL form, built at upload (device_csr.hip.h, build_sell)
+    const unsigned*      sell_code;   // per slot: value index << sell_obits | column - the slice's base; slot k of a slice's 64 rows contiguous
+    const int*           sell_sptr;   // per slice (+ 1): its first slot row (units of 64 slots); the difference is the slice's longest row
+    const int*           sell_sbase;  // per slice: its smallest column
+    const unsigned char* sell_rlen;   // per row: its length
+    const double*        sell_tab;    // the distinct values
+    int                  sell_nv, sell_obits;
 };
 
 __device__ __forceinline__ void zx_store(const CsrArgs& a, int r, double s)

@@ -42,6 +42,7 @@
 #include "kernels.hip.h"
 #include "kernels2.hip.h"
 #include "kernels3.hip.h"
+#include "kernels4.hip.h"
 #include "small_solvers.hip.h"
 #include "seq_split.hip.h"
 #include "seq_chain.hip.h"
@@ -584,6 +585,10 @@ int fasp_hip_amg_kernel_info(const fasp_hip_amg* h, int level, int which, int* k
     else if (k == 2 && g_tune.gen2 >= 2 && g_tune.xtile && M.lja16 && M.wrows == 64 && M.wcap == 512) {   // k_csr_xtile
         k = 10;
         bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + 4.0 * M.ntcols + 4.0 * ((M.row + 63) / 64 + 1.0);   // values + 16-bit positions + the tiles' column lists
+    }
+    else if (k == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512) {   // 11 = k_csr_sell (kernels4.hip.h): words + row lengths + slice table + value table
+        k = 11;
+        bytes = 4.0 * (double)M.sell_slots + 1.0 * M.row + 4.0 * (2.0 * M.sell_nslice + 1.0) + 8.0 * M.sell_nv;
     }
     else if (k == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512) k = 8;   // k_csr_wstream2
     if (kind) *kind = k;
@@ -2248,6 +2253,7 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "renumber_chunk")) g_tune.renumber_chunk = value; // rows per chunk inside which the balls grow (reorder.cpp)
     else if (!std::strcmp(key, "time_cold")) g_time_cold = value;
     else if (!std::strcmp(key, "estream")) g_tune.estream = value;   // long-row operators: the entry-parallel stream kernel where it measured faster (1, default: mean rows below 256 entries), wherever its tables exist (2), never (0: the row kernel); read at launch
+    else if (!std::strcmp(key, "sell")) g_tune.sell = value;         // value-indexed sliced-ELL form where an operator has it (1, default) or its plain-CSR kernels (0), the other codings untouched; read at launch
     else if (!std::strcmp(key, "es_dbg")) g_tune.es_dbg = value;     // (FASP_LAB_DEBUG builds: parts of the stream kernel switched off -- timings only)
     else if (!std::strcmp(key, "pcg_dev_beta")) g_tune.pcg_dev_beta = value;   // top-level PCG: (z, r), beta and alpha stay on the device, one host wait per iteration (1, default) or two (0)
     else if (!std::strcmp(key, "seq_chain_touch")) g_tune.seq_chain_touch = value;   // chain form: blocks by which a workgroup of its own on the chain's XCD touches the band planes ahead (8; 0: the importer wave does, four ahead)
@@ -2263,6 +2269,25 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "wrows")) g_tune.wrows = value;
     else if (!std::strcmp(key, "wcap")) g_tune.wcap = value;
     else return ERROR_INPUT_PAR;
+    return FASP_SUCCESS;
+}
+
+// CPU test entry: the sliced-ELL coding of A as upload_csr would build it (device_csr.hip.h, build_sell), decoded again and walked on the host
+int fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double* bytes, int* ia_out, int* ja_out, double* val_out, const double* x, double* y)
+{
+    if (!A || !info || A->row < 0 || A->nnz < 0) return ERROR_INPUT_PAR;
+    HostCSR M;
+    M.row = A->row; M.col = A->col; M.nnz = A->nnz;
+    M.ia.view(A->IA, (size_t)A->row + 1); M.ja.view(A->JA, (size_t)std::max(A->nnz, 1)); M.val.view(A->val, (size_t)std::max(A->nnz, 1));
+    SellHost S;
+    int why = 0;
+    const bool ok = build_sell(M, S, cap_percent > 0 ? cap_percent : SELL_CAP_PERCENT, &why);
+    info[0] = ok ? 1 : 0; info[1] = why; info[2] = S.nv; info[3] = S.vbits; info[4] = S.obits; info[5] = S.nslice;
+    info[6] = ok ? (int)std::min<long long>(S.slots / 64, 0x7fffffff) : 0; info[7] = SELL_MAXV;
+    if (bytes) *bytes = ok ? S.bytes(M.row) : 0.0;
+    if (!ok) return FASP_SUCCESS;
+    if (ia_out && ja_out && val_out) sell_decode_host(S, M.row, ia_out, ja_out, val_out);
+    if (x && y) sell_mxv_host(S, M.row, x, y);
     return FASP_SUCCESS;
 }
 
@@ -2379,6 +2404,88 @@ double fasp_hip_time_kernel(fasp_hip_amg* h, int kind, int level, int reps)
 }
 
 
+// Test entry: one row operation of launch_csr on an operator of a resident level, with the vectors given and returned on the host.
+// which: 0 A, 1 P, 2 R.  op: the RowOp codes (0 y = M x, 1 y = b - M x, 2 y += M x, 3 y -= M x, 4 y += scalar M x, 5 Jacobi sweep with weight
+// scalar (A only), 6 L1-diagonal sweep (A only), 7 y = M x with (y, b)), or 8: y = M x with the first Jacobi sweep of the level the result is
+// the right-hand side of written along, y2_i = scalar y_i / b_i.  x: M.col values (ops 5, 6: the iterate); b, y, y2: M.row values.
+// red (may be NULL): ops 7 and 5 -- the finished sum of the fused partials, (y, b) or (x_new, b); NaN when the kernel did not produce them.
+static int row_op_host(DevLevel& D, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red)
+{
+    if (which < 0 || which > 2 || op < 0 || op > 8 || !x || !y) return ERROR_INPUT_PAR;
+    const DevCSR& M = which == 0 ? D.A : which == 1 ? D.P : D.R;
+    if (!M.ia || ((op == 5 || op == 6) && which != 0) || ((op == 1 || op >= 5) && !b) || (op == 8 && !y2)) return ERROR_INPUT_PAR;
+    const size_t nr = (size_t)std::max(M.row, 1), nc = (size_t)std::max(M.col, 1);
+    double *dx = nullptr, *db = nullptr, *dy = nullptr, *dy2 = nullptr;
+    int st = FASP_SUCCESS;
+    auto run = [&]() -> int {
+        HIPCK(hipMalloc(&dx, 8 * nc)); HIPCK(hipMalloc(&db, 8 * nr)); HIPCK(hipMalloc(&dy, 8 * nr)); HIPCK(hipMalloc(&dy2, 8 * nr));
+        HIPCK(hipMemcpy(dx, x, 8 * (size_t)M.col, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(dy, y, 8 * (size_t)M.row, hipMemcpyHostToDevice));
+        if (b) HIPCK(hipMemcpy(db, b, 8 * (size_t)M.row, hipMemcpyHostToDevice));
+        CsrArgs a{};
+        a.x = dx; a.y = dy; a.b = db;
+        int G = 0;
+        bool have_red = false;
+        switch (op) {
+            case 0: G = launch_csr<OP_MXV>(M, a); break;
+            case 1: G = launch_csr<OP_RESID>(M, a); break;
+            case 2: G = launch_csr<OP_ADD>(M, a); break;
+            case 3: G = launch_csr<OP_SUB>(M, a); break;
+            case 4: a.alpha = scalar; G = launch_csr<OP_AXPY>(M, a); break;
+            case 5:
+                a.diag = D.diag; a.omega = scalar;
+                if (red) { a.partials = g_ctx.d_partials; g_jacobi_dot_done = false; }
+                G = launch_csr<OP_JACOBI>(M, a);
+                have_red = red && g_jacobi_dot_done;
+                g_jacobi_dot_done = false;
+                break;
+            case 6: a.diag = D.l1; a.omega = scalar; G = launch_csr<OP_L1DIAG>(M, a); break;
+            case 7: a.b = nullptr; a.dotv = db; a.partials = g_ctx.d_partials; G = launch_csr<OP_MXV_DOT>(M, a); have_red = red != nullptr; break;
+            default: a.b = nullptr; a.zx = dy2; a.zdiag = db; a.zomega = scalar; G = launch_csr<OP_MXV>(M, a); break;
+        }
+        if (red) *red = std::nan("");
+        if (have_red) {
+            d_finalize(G, 1, 0u, 0, false);
+            if (fetch_red(0, 1, red) < 0) return ERROR_MISC;
+        }
+        HIPCK(hipStreamSynchronize(g_ctx.stream));
+        HIPCK(hipMemcpy(y, dy, 8 * (size_t)M.row, hipMemcpyDeviceToHost));
+        if (op == 8) HIPCK(hipMemcpy(y2, dy2, 8 * (size_t)M.row, hipMemcpyDeviceToHost));
+        return FASP_SUCCESS;
+    };
+    st = run();
+    (void)hipFree(dx); (void)hipFree(db); (void)hipFree(dy); (void)hipFree(dy2);
+    return st;
+}
+
+int fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red)
+{
+    FASP_ENTRY();
+    if (!h || level < 0 || level >= (int)h->L.size()) return ERROR_INPUT_PAR;
+    return row_op_host(h->L[level], which, op, x, b, y, y2, scalar, red);
+}
+// ... and of a matrix given on the host, uploaded the way a level's A is (coding, kernel selection, diagonal tables)
+int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out)
+{
+    FASP_ENTRY();
+    if (!A || ctx_init() < 0) return ERROR_INPUT_PAR;
+    HostCSR M;
+    M.row = A->row; M.col = A->col; M.nnz = A->nnz;
+    M.ia.view(A->IA, (size_t)A->row + 1); M.ja.view(A->JA, (size_t)std::max(A->nnz, 1)); M.val.view(A->val, (size_t)std::max(A->nnz, 1));
+    DevLevel D;
+    int st;
+    {
+        HostThreads team;
+        st = upload_csr(M, D.A);
+        if (st >= 0 && M.row == M.col) st = upload_diag(M, D);
+    }
+    if (st >= 0 && (op == 5 || op == 6) && !D.diag) st = ERROR_INPUT_PAR;
+    if (st >= 0) st = row_op_host(D, 0, op, x, b, y, y2, scalar, red);
+    if (kind_out) *kind_out = (D.A.kind == 2 && sell_active(D.A)) ? 11 : D.A.kind;
+    free_level(D);
+    return st;
+}
+
 // Development / test entry: one operator through the resident upload path (lossless coding, kernel selection as for a
 // hierarchy level) timed with HIP events on the launch stream.  op: 0 y = A x, 1 y -= A x, 2 Jacobi sweep, 5 y = A x
 // fused with (y, x).  Returns milliseconds per launch (< 0: error); *kind_out = kernel family as fasp_hip_amg_kernel_info.
@@ -2425,6 +2532,7 @@ double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out)
         int k = D.kind;
         if (D.code && g_tune.compress) k = 4;
         if (D.pat && g_tune.compress) k = (D.nxrows >= 0 && g_tune.gen2) ? (D.rowbase ? 9 : 6) : 5;
+        if (k == 2 && sell_active(D) && (double)D.nnz > 7.6 * D.row) k = 11;
         *kind_out = k;
     }
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(w); (void)hipFree(dg);

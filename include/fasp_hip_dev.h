@@ -123,6 +123,20 @@ int fasp_hip_dist_get_list(const fasp_hip_amg* h, int level, int which, ivector*
  * kernel walks them: 0 when every entry is covered once and every row is finished exactly once, else the negative number of the check
  * that failed.  info (may be NULL) = {wave ranges, chunks, rows cut by a wave boundary}.  No GPU needed. */
 int  fasp_hip_estream_selftest(const int* ia, int nrow, int nnz, int per_wave, int wmax, int* info);
+/* The value-indexed sliced-ELL coding of k_csr_sell (csrc/kernels4.hip.h) built on the HOST as an upload would build it.  cap_percent: largest
+ * slots / entries accepted, in percent (<= 0: the product's 125).  info[8] = {coded (1 / 0), why not (0 coded, 1 size or mean row length outside the
+ * range served, 2 a row beyond 255 entries, 3 padding over the cap, 4 too many distinct values, 5 index + offset beyond 32 bits), distinct values,
+ * index bits, offset bits, slices, slot rows of 64, largest table accepted}; *bytes = what one pass over the coded form reads.  When coded and the
+ * pointers are given: ia_out / ja_out / val_out = the form decoded back to CSR (sized like A's arrays), y = A x over the coded form in the kernel's
+ * order (slice by slice, every row left to right).  No GPU needed. */
+int  fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double* bytes, int* ia_out, int* ja_out, double* val_out, const double* x, double* y);
+/* test entry: one row operation of the kernel family that serves operator `which` (0 A, 1 P, 2 R) of a resident level, vectors given and returned
+ * on the host.  op: 0 y = M x, 1 y = b - M x, 2 y += M x, 3 y -= M x, 4 y += scalar M x, 5 Jacobi sweep with weight scalar (A only; x is the
+ * iterate), 6 L1-diagonal sweep (A only), 7 y = M x fused with (y, b), 8 y = M x with y2_i = scalar y_i / b_i written along (the fused first Jacobi
+ * sweep of the next level).  red (may be NULL): the finished fused sum of ops 7 and 5 -- (y, b), (x_new, b); NaN where the kernel has none. */
+int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red);
+/* ... and of a matrix given on the host, uploaded the way a level's A is; *kind_out (may be NULL) = 11 when its sliced-ELL form is in use */
+int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
