@@ -56,6 +56,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_hip_ilu_resident_count", "fasp_hip_ilu_time",
     "fasp_ilu_dbsr_setup", "fasp_precond_dbsr_ilu", "fasp_solver_dbsr_krylov_ilu", "fasp_smoother_dbsr_ilu",
     "fasp_fwrapper_dbsr_krylov_ilu_",
+    "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
 ]
 
 
@@ -243,6 +244,11 @@ def lib():
     L.fasp_fwrapper_dbsr_krylov_ilu_.argtypes = [P(C.c_int), P(C.c_int), P(C.c_int), T.c_int_p, T.c_int_p, T.c_double_p,
                                                  T.c_double_p, T.c_double_p, P(C.c_double), P(C.c_int), P(C.c_int)]
     L.fasp_fwrapper_dbsr_krylov_ilu_.restype = None
+    # ILU smoothing in the block AMG cycle (AMG_param.ILU_levels > 0): the factors a block hierarchy owns
+    L.fasp_hip_bsr_amg_get_ilu.argtypes = [C.c_void_p, C.c_int, P(T.ILU_data)]
+    L.fasp_hip_bsr_amg_ilu_info.argtypes = [C.c_void_p, C.c_int, T.c_double_p]
+    L.fasp_hip_bsr_amg_ilu_smooth_time.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.fasp_hip_bsr_amg_ilu_smooth_time.restype = C.c_double
     return L
 
 
@@ -557,6 +563,32 @@ class BSRAMG:
         v = T.dBSRmat()
         lib().fasp_hip_bsr_amg_get_matrix(self.h, level, 0, C.byref(v))
         return np.ctypeslib.as_array(p, (v.ROW * v.nb * v.nb,)).copy()
+
+    def ilu(self, level):
+        """The host ILU factor of a level below AMG_param.ILU_levels (fasp_hip_bsr_amg_get_ilu) -> dict(nb, row, nzlu, ijlu,
+        luval) of copies, or None when the level has none."""
+        d = T.ILU_data()
+        st = lib().fasp_hip_bsr_amg_get_ilu(self.h, level, C.byref(d))
+        if st < 0:
+            raise IndexError(level)
+        if st == 0:
+            return None
+        return {"nb": d.nb, "row": d.row, "nzlu": d.nzlu,
+                "ijlu": np.ctypeslib.as_array(d.ijlu, (d.nzlu,)).copy(),
+                "luval": np.ctypeslib.as_array(d.luval, (d.nzlu * d.nb * d.nb,)).copy()}
+
+    def ilu_info(self, level):
+        """Schedule of the level's device factor (fasp_hip_bsr_amg_ilu_info): (levels of L, of U, form of the L solve, of the
+        U solve -- 1 single launch, 0 level launches --, chunks of L, of U), or None when the level has no device factor."""
+        info = np.zeros(6)
+        st = lib().fasp_hip_bsr_amg_ilu_info(self.h, level, T.dp(info))
+        if st < 0:
+            raise IndexError(level)
+        return tuple(int(v) for v in info) if st else None
+
+    def ilu_smooth_time(self, level=0, reps=20):
+        """Microseconds per ILU smoothing step of the cycle on `level` (fasp_hip_bsr_amg_ilu_smooth_time)."""
+        return lib().fasp_hip_bsr_amg_ilu_smooth_time(self.h, level, reps)
 
     def solve(self, b, itparam, x0=None, hist_cap=1200):
         """Krylov solve on the resident block hierarchy -> (status, x, hist, stats)."""

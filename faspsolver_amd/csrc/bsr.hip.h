@@ -57,8 +57,15 @@ using namespace fasp_bsr;
 // BSR AMG hierarchy resident in HBM (config 3): unsmoothed aggregation, block-Jacobi
 // V/W cycle (PreMGCycle.c:287), GMRES on the coarsest level, Krylov drivers shared with CSR
 // ---------------------------------------------------------------------------
+// ilu.hip.h (included further down in solver.hip): the device copy of an ILU factor
+namespace {
+struct IluDev;
+void    ilu_dev_destroy(IluDev* D);
+IluDev* ilu_upload(const ILU_data* d, int nb, int* st);
+}  // namespace
 struct BsrLevel {
     std::unique_ptr<TmpBSR> A, P, R;
+    IluDev* ilu = nullptr;  // levels below ILU_levels: the resident factor the cycle smooths with (schedule, slabs, work vectors)
     double *dinv = nullptr, *b = nullptr, *x = nullptr, *x2 = nullptr, *w = nullptr;
     int  n = 0;  // scalar rows (owned)
     bool x_zero = false;
@@ -190,6 +197,18 @@ static int bsr_smooth(fasp_hip_amg_bsr* h, int level, bool post, int smoother, i
     return st;
 }
 
+// Smoothing of level l in the cycle.  A level with an ILU factor (l < ILU_levels of level 0, PreMGCycle.c:321-326 and
+// :508-512): one ILU step -- also when steps == 0 -- then `steps` block Gauss-Seidel sweeps, ascending before the coarse
+// correction and descending after it, whatever param.smoother says.  Other levels: the caller's smoother.
+static int bsr_ilu_smooth(fasp_hip_amg_bsr* h, int level);   // ilu.hip.h
+static int bsr_smooth_level(fasp_hip_amg_bsr* h, int l, bool post, const AMG_param& param, int steps)
+{
+    if (l >= h->H.L[0].ILU_levels || !h->L[l].ilu) return bsr_smooth(h, l, post, param.smoother, steps, param.relaxation);
+    int st = bsr_ilu_smooth(h, l);
+    for (int i = 0; i < steps && st >= 0; ++i) st = bsr_seq_sweep(h, l, post, false, 0.0);
+    return st;
+}
+
 static KOps bsr_ops(fasp_hip_amg_bsr* h, int level, int set);
 
 // ghost entries of a vector of a row-partitioned block level from their owners (hierarchy.hip.h, halo_exchange: the same
@@ -226,7 +245,7 @@ ForwardSweep:
     while (l < nl - 1) {
         BsrLevel& Lv = h->L[l];
         ++nu_l[l];
-        { const int st = bsr_smooth(h, l, false, param.smoother, steps, param.relaxation); if (st < 0) return st; }
+        { const int st = bsr_smooth_level(h, l, false, param, steps); if (st < 0) return st; }
         if (Lv.x_zero) { HIPCK(hipMemsetAsync(Lv.x, 0, sizeof(double) * Lv.nv, s)); Lv.x_zero = false; }
         if (bsr_halo(Lv, Lv.x) < 0) return ERROR_MISC;
         bsr_resid(*Lv.A, Lv.x, Lv.b, Lv.w);
@@ -306,7 +325,7 @@ ForwardSweep:
             launch_bsr<1>(*Lv.P, a);
         }
         // the reference post-smooths `steps` = presmooth_iter times (:543)
-        { const int st = bsr_smooth(h, l, true, param.smoother, steps, param.relaxation); if (st < 0) return st; }
+        { const int st = bsr_smooth_level(h, l, true, param, steps); if (st < 0) return st; }
         if (nu_l[l] < cycle_type) break;
         nu_l[l] = 0;
     }

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/fasp_hip.h"
@@ -178,10 +179,20 @@ struct HostBSR {
     }
 };
 struct DistLocalBSR { HostBSR A, P, R; };   // local rows of a distributed block level, local block-column numbering
+// block ILU factor of a level (fasp_ilu_dbsr_setup, ilu_setup.cpp), freed with the hierarchy
+struct HostILU {
+    ILU_data d;
+    HostILU() { std::memset(&d, 0, sizeof(d)); }
+    HostILU(const HostILU&)            = delete;
+    HostILU& operator=(const HostILU&) = delete;
+    ~HostILU() { fasp_ilu_data_free(&d); }
+};
 struct HostLevelBSR {
     HostBSR     A, P, R;
     Buf<double> diaginv;  // inverse diagonal blocks of A (levels that are smoothed)
     bool        has_coarse = false;
+    std::unique_ptr<HostILU> LU;   // levels below AMG_param.ILU_levels: the factor the cycle smooths with (PreAMGSetupUABSR.c:166)
+    int         ILU_levels = 0;    // mgl[lvl].ILU_levels of the reference: param->ILU_levels - lvl after the setup
 };
 struct HostHierarchyBSR {
     std::vector<HostLevelBSR> L;

@@ -2342,6 +2342,17 @@ int host_setup_ua_bsr(const dBSRmat* A, AMG_param* param, HostHierarchyBSR& H)
     H.L.emplace_back();
     copy_bsr(A, H.L[0].A);
     if (prtlvl > PRINT_NONE) std::printf("\nSetting up UA AMG (BSR) ...\n");
+    // :149-158: the factor's parameters come from the AMG_param (ILU_permtol is never set; block ILUk does not read it)
+    const int ilu_levels_in = param->ILU_levels;
+    ILU_param iluparam;
+    std::memset(&iluparam, 0, sizeof(iluparam));
+    if (param->ILU_levels > 0) {
+        iluparam.print_level = param->print_level;
+        iluparam.ILU_lfil    = param->ILU_lfil;
+        iluparam.ILU_droptol = param->ILU_droptol;
+        iluparam.ILU_relax   = param->ILU_relax;
+        iluparam.ILU_type    = param->ILU_type;
+    }
     if (param->aggregation_type == PAIRWISE) param->pair_number = std::min<int>(param->pair_number, max_levels);  // :163
 
     int lvl = 0;
@@ -2350,6 +2361,18 @@ int host_setup_ua_bsr(const dBSRmat* A, AMG_param* param, HostHierarchyBSR& H)
             HostLevelBSR& Lv = H.L[lvl];
             const int nb = Lv.A.nb;
             const size_t nb2 = (size_t)nb * nb;
+            if (lvl < param->ILU_levels) {   // :166-176: the level's A in its own numbering; a failure ends ILU from here on
+                Lv.LU.reset(new HostILU);
+                dBSRmat v = Lv.A.view();
+                if (fasp_ilu_dbsr_setup(&v, &Lv.LU->d, &iluparam) < 0) {
+                    if (prtlvl > PRINT_MIN) {
+                        std::printf("### WARNING: ILU setup on level-%d failed!\n", lvl);
+                        std::printf("### WARNING: Disable ILU for level >= %d.\n", lvl);
+                    }
+                    param->ILU_levels = (short)lvl;
+                    Lv.LU.reset();
+                }
+            }
             Lv.diaginv.alloc((size_t)Lv.A.ROW * nb2);
             { dBSRmat v = Lv.A.view(); if ((status = bsr_diaginv(&v, Lv.diaginv.data())) < 0) return status; }
             HostCSR S, N;
@@ -2396,6 +2419,10 @@ int host_setup_ua_bsr(const dBSRmat* A, AMG_param* param, HostHierarchyBSR& H)
         std::printf("### ERROR: fasp_hip: host allocation failed during AMG setup\n");
         return ERROR_ALLOC_MEM;
     }
+    // :149 / :351: level 0 keeps the caller's value, the levels below it count down from the value after the loop (lower
+    // where a factorisation failed).  The cycle smooths with ILU exactly where a factor exists.
+    H.L[0].ILU_levels = ilu_levels_in;
+    for (size_t l = 1; l < H.L.size(); ++l) H.L[l].ILU_levels = param->ILU_levels - (int)l;
     H.setup_seconds = wall_seconds() - t0;
     if (prtlvl > PRINT_NONE)
         std::printf("Unsmoothed aggregation (BSR) setup costs %.4f seconds, %d levels.\n", H.setup_seconds, lvl + 1);
@@ -2418,8 +2445,8 @@ int check_supported_bsr(const ITS_param* it, const AMG_param* amg, int nb)
             std::printf("### ERROR: fasp_hip: BSR aggregation_type %d not supported (VMB and symmetric pairwise matching only)\n", amg->aggregation_type);
             return ERROR_INPUT_PAR;
         }
-        if (amg->ILU_levels > 0 || amg->SWZ_levels > 0) {
-            std::printf("### ERROR: fasp_hip: ILU / Schwarz smoothers have no device path\n");
+        if (amg->SWZ_levels > 0) {
+            std::printf("### ERROR: fasp_hip: Schwarz smoothers have no device path\n");
             return ERROR_INPUT_PAR;
         }
         switch (amg->smoother) {  // the five smoothers of fasp_solver_mgcycle_bsr (PreMGCycle.c:327-365)

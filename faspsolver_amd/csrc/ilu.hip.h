@@ -26,6 +26,10 @@
 //
 // Block factors (fasp_ilu_dbsr_setup, PreBSR.c:347) run through the same schedule with NB x NB blocks per entry (the kernels
 // are templated on NB, NB = 1 being the scalar factor): see ilu_chunk for the slab layout and the order of operations.
+//
+// The smoother of the block AMG cycle (bsr_ilu_smooth, ItrSmootherBSR.c:1479: x = x + (LU)^-1 (b - A x)) runs on a factor the
+// hierarchy owns and ends its U solve with the EPI form of the kernels: the lane that finishes z_row also writes
+// x_row = x_row + z_row (0.0 + z_row from a zero guess), which saves the separate axpy pass and its read of z.
 
 #ifndef ILU_FLOW_MIN_LEVELS
 #define ILU_FLOW_MIN_LEVELS 24
@@ -44,6 +48,8 @@ struct IluArgs {
     double*          out;     // solution (indexed by row)
     unsigned*        sync;    // single launch: [0] ticket, [1] error word, [6..7] host-mapped error word (flow_give_up)
     int              nchunk;
+    double*          x;       // EPI kernels only: the iterate, x_row = x_row + out_row written with out_row
+    int              x_zero;  // ... from a zero guess: x_row = 0.0 + out_row, x is not read
 };
 
 // one row of an NB x NB block times NB values, the row's elements 64 doubles apart (one slab plane each), summed left to
@@ -61,7 +67,9 @@ __device__ __forceinline__ double ilu_block_row(const double* a, const double* x
 // an NB x NB block whose element (p, q) lies at vals[(cbase + 64 k) NB^2 + (p NB + q) 64 + lane] (NB^2 planes, each one
 // coalesced wavefront load); U's inverse diagonal blocks lie in NB^2 planes of 64 per chunk the same way.  Per entry the
 // lane forms mult_p = (L_ij x_j)_p and subtracts it, acc_p = acc_p - mult_p (PreBSR.c:347); U ends with z = D^-1 acc.
-template <int NB, bool HAS_D, bool SPIN>
+// EPI (the last stage of the smoother, U only): the finished value is also added to the iterate, x = x + z -- a plain store:
+// nobody waits for x; out still gets z (the single launch publishes it to the rows that spin on it).
+template <int NB, bool HAS_D, bool SPIN, bool EPI = false>
 __device__ __forceinline__ void ilu_chunk(const IluArgs& a, int c, int lane)
 {
     typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -113,18 +121,23 @@ __device__ __forceinline__ void ilu_chunk(const IluArgs& a, int c, int lane)
         if (SPIN) __hip_atomic_store((gu64*)dst, (unsigned long long)__double_as_longlong(acc[p]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *dst = acc[p];
     }
+    if (EPI) {
+        double* xr = a.x + (long long)row * NB;
+#pragma unroll
+        for (int p = 0; p < NB; ++p) xr[p] = (a.x_zero ? 0.0 : xr[p]) + acc[p];   // 0.0 + (-0.0) = +0.0, as the reference's sum gives
+    }
 }
 
 // one level: chunks [c0, c1), four wavefronts per workgroup, one chunk each
-template <int NB, bool HAS_D>
+template <int NB, bool HAS_D, bool EPI = false>
 __global__ __launch_bounds__(256) void k_ilu_level(IluArgs a, int c0, int c1)
 {
     const int c = c0 + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (c < c1) ilu_chunk<NB, HAS_D, false>(a, c, (int)(threadIdx.x & 63));
+    if (c < c1) ilu_chunk<NB, HAS_D, false, EPI>(a, c, (int)(threadIdx.x & 63));
 }
 
 // all levels in one launch: wavefronts draw chunks in level order
-template <int NB, bool HAS_D>
+template <int NB, bool HAS_D, bool EPI = false>
 __global__ __launch_bounds__(256) void k_ilu_flow(IluArgs a)
 {
     typedef __attribute__((address_space(1))) unsigned gu32;
@@ -134,7 +147,7 @@ __global__ __launch_bounds__(256) void k_ilu_flow(IluArgs a)
         if (lane == 0) c = (int)__hip_atomic_fetch_add((gu32*)a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         c = __shfl(c, 0);
         if (c >= a.nchunk) break;
-        ilu_chunk<NB, HAS_D, true>(a, c, lane);
+        ilu_chunk<NB, HAS_D, true, EPI>(a, c, lane);
     }
 }
 
@@ -303,26 +316,31 @@ bool ilu_single_launch(const IluTri& T)
 template <int NB>
 void ilu_launch(const IluTri& T, bool upper, bool single, const IluArgs& a)
 {
+    const bool epi = upper && a.x != nullptr;
     if (single) {
         const int grid = std::max(1, std::min((T.nchunk + 3) / 4, 1024));
-        if (upper) hipLaunchKernelGGL((k_ilu_flow<NB, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
+        if (epi) hipLaunchKernelGGL((k_ilu_flow<NB, true, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
+        else if (upper) hipLaunchKernelGGL((k_ilu_flow<NB, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
         else hipLaunchKernelGGL((k_ilu_flow<NB, false>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
         return;
     }
     for (int l = 0; l < T.nlev; ++l) {
         const int c0 = T.lvl_chunk[(size_t)l], c1 = T.lvl_chunk[(size_t)l + 1];
         const dim3 grid((unsigned)((c1 - c0 + 3) / 4));
-        if (upper) hipLaunchKernelGGL((k_ilu_level<NB, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+        if (epi) hipLaunchKernelGGL((k_ilu_level<NB, true, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
+        else if (upper) hipLaunchKernelGGL((k_ilu_level<NB, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
         else hipLaunchKernelGGL((k_ilu_level<NB, false>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
     }
 }
 
-// out = T^-1 in (in, out: device vectors of n nb, not the same)
-int ilu_tri_solve(IluDev* D, const IluTri& T, bool upper, const double* in, double* out)
+// out = T^-1 in (in, out: device vectors of n nb, not the same).  x (U only, may be nullptr; not in or out): x = x + out
+// written by the same kernels, x = 0.0 + out when x_zero.
+int ilu_tri_solve(IluDev* D, const IluTri& T, bool upper, const double* in, double* out, double* x = nullptr, bool x_zero = false)
 {
     IluArgs a{};
     a.rows = T.rows; a.len = T.len; a.cbase = T.cbase; a.cols = T.cols; a.vals = T.vals; a.diag = T.diag;
     a.in = in; a.out = out; a.sync = D->sync; a.nchunk = T.nchunk;
+    a.x = upper ? x : nullptr; a.x_zero = x_zero ? 1 : 0;
     if (T.nchunk == 0) return FASP_SUCCESS;
     const bool single = ilu_single_launch(T);
     if (single) {
@@ -451,7 +469,87 @@ void ilu_register_host(ILU_data* d, int block_nb)
 }
 }  // namespace fasp
 
+namespace fasp_bsr {
+// The ILU step of the block cycle on level `level` (fasp_smoother_dbsr_ilu, ItrSmootherBSR.c:1479) with the factor the
+// hierarchy owns: r = b - A x by the level's residual kernel (a zero guess: r = b, no product), y = L^-1 r, then the U solve
+// that writes z and x = x + z together.  fasp_hip_tune("ilu_smooth_fused", 0): the three passes it replaces (residual, both
+// solves, axpy) -- the same bits, kept for the A/B measurement of tools/perf_bilu.py.
+static int bsr_ilu_smooth(fasp_hip_amg_bsr* h, int level)
+{
+    BsrLevel& Lv = h->L[level];
+    IluDev* D = Lv.ilu;
+    if (!D || !Lv.replicated) return ERROR_INPUT_PAR;   // a triangular solve couples all rows: whole levels only
+    if (seq_err_pending()) return seq_err_check();
+    const bool zero = Lv.x_zero;
+    const double* rhs = Lv.b;
+    if (!zero) { bsr_resid(*Lv.A, Lv.x, Lv.b, D->r); rhs = D->r; }
+    int st = ilu_tri_solve(D, D->L, false, rhs, D->y);
+    if (st < 0) return st;
+    if (g_tune.ilu_smooth_fused) {
+        st = ilu_tri_solve(D, D->U, true, D->y, D->z, Lv.x, zero);
+    } else {
+        st = ilu_tri_solve(D, D->U, true, D->y, D->z);
+        if (st >= 0 && zero) HIPCK(hipMemsetAsync(Lv.x, 0, sizeof(double) * Lv.n, g_ctx.stream));
+        if (st >= 0) d_axpy(Lv.n, 1.0, D->z, Lv.x);
+    }
+    Lv.x_zero = false;
+    return st;
+}
+}  // namespace fasp_bsr
+
 }  // extern "C++"
+
+// test entries (fasp_hip_dev.h): the host factor of a level of a block hierarchy, and the schedule of its device copy
+int fasp_hip_bsr_amg_get_ilu(const fasp_hip_amg_bsr* h, int level, ILU_data* view)
+{
+    FASP_ENTRY();
+    if (!h || !view || level < 0 || level >= (int)h->H.L.size()) return ERROR_INPUT_PAR;
+    const HostLevelBSR& L = h->H.L[level];
+    if (!L.LU) return 0;
+    *view = L.LU->d;
+    return 1;
+}
+
+int fasp_hip_bsr_amg_ilu_info(const fasp_hip_amg_bsr* h, int level, double info[6])
+{
+    FASP_ENTRY();
+    if (!h || !info || level < 0 || level >= (int)h->H.L.size()) return ERROR_INPUT_PAR;
+    for (int i = 0; i < 6; ++i) info[i] = 0.0;
+    const IluDev* D = level < (int)h->L.size() ? h->L[level].ilu : nullptr;
+    if (!D) return 0;
+    info[0] = D->L.nlev; info[1] = D->U.nlev;
+    info[2] = ilu_single_launch(D->L) ? 1 : 0; info[3] = ilu_single_launch(D->U) ? 1 : 0;
+    info[4] = D->L.nchunk; info[5] = D->U.nchunk;
+    return 1;
+}
+
+// measurement entry (fasp_hip_dev.h): microseconds per ILU smoothing step of the cycle on `level`, from a non-zero iterate
+// (b_i = sin(0.37 i) + 0.1, x restored to zero afterwards), in the form fasp_hip_tune("ilu_smooth_fused", ..) selects
+double fasp_hip_bsr_amg_ilu_smooth_time(fasp_hip_amg_bsr* h, int level, int reps)
+{
+    FASP_ENTRY();
+    if (!h || level < 0 || level >= (int)h->L.size() || !h->L[level].ilu || reps <= 0) return -1.0;
+    BsrLevel& Lv = h->L[level];
+    std::vector<double> hb((size_t)Lv.n);
+    for (size_t i = 0; i < hb.size(); ++i) hb[i] = std::sin(0.37 * (double)i) + 0.1;
+    if (hipMemcpy(Lv.b, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice) != hipSuccess) return -1.0;
+    Lv.x_zero = true;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
+    if (bsr_ilu_smooth(h, level) < 0) return -1.0;   // warm-up; the timed steps start from its iterate
+    (void)hipEventRecord(e0, g_ctx.stream);
+    for (int i = 0; i < reps; ++i) (void)bsr_ilu_smooth(h, level);
+    (void)hipEventRecord(e1, g_ctx.stream);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    (void)hipMemsetAsync(Lv.b, 0, sizeof(double) * (size_t)Lv.nv, g_ctx.stream);
+    (void)hipMemsetAsync(Lv.x, 0, sizeof(double) * (size_t)Lv.nv, g_ctx.stream);
+    (void)hipStreamSynchronize(g_ctx.stream);
+    if (seq_err_check() < 0) return -1.0;
+    return 1000.0 * ms / reps;
+}
 
 void fasp_precond_ilu(double* r, double* z, void* data)
 {

@@ -978,6 +978,7 @@ void fasp_hip_bsr_amg_destroy(fasp_hip_amg_bsr* h)
         for (auto& sc : Lv.sched) sc.release();
         if (Lv.d_send_idx) (void)hipFree(Lv.d_send_idx);
         if (Lv.d_sendbuf) (void)hipFree(Lv.d_sendbuf);
+        ilu_dev_destroy(Lv.ilu);
     }
     double* v[] = {h->b, h->u, h->p, h->t, h->r};
     for (double* q : v) if (q) (void)hipFree(q);
@@ -1012,6 +1013,10 @@ int fasp_hip_bsr_amg_create(fasp_hip_amg_bsr** out, const dBSRmat* A, AMG_param*
     int st = check_supported_bsr(nullptr, amgparam, A->nb);
     if (st < 0) return st;
     if ((st = ctx_init()) < 0) return st;
+    if (amgparam->ILU_levels > 0 && comm_size() > 1) {   // a triangular solve couples all rows of a level
+        std::printf("### ERROR: fasp_hip: ILU smoothing (ILU_levels > 0) has no multi-GPU path\n");
+        return ERROR_INPUT_PAR;
+    }
     fasp_hip_amg_bsr* h = nullptr;
     if ((st = fasp_hip_bsr_amg_create_host(&h, A, amgparam)) < 0) return st;
     const int nl = (int)h->H.L.size();
@@ -1050,6 +1055,11 @@ int fasp_hip_bsr_amg_create(fasp_hip_amg_bsr** out, const dBSRmat* A, AMG_param*
             const size_t nd = (size_t)Lv.nloc * nb2;
             if (hipMalloc(&Lv.dinv, sizeof(double) * std::max<size_t>(nd, 1)) != hipSuccess) ok = false;
             else (void)hipMemcpy(Lv.dinv, HL.diaginv.data() + (size_t)Lv.row0 * nb2, sizeof(double) * nd, hipMemcpyHostToDevice);
+        }
+        if (ok && HL.LU && !DL) {   // the level's factor, resident with the hierarchy (not through the host-pointer registry)
+            int ist;
+            Lv.ilu = ilu_upload(&HL.LU->d, nb, &ist);
+            if (!Lv.ilu) { fasp_hip_bsr_amg_destroy(h); return ist < 0 ? ist : ERROR_ALLOC_MEM; }
         }
         if (ok && DL) {   // halo lists, expanded from blocks to scalars
             const int P = comm_size();
@@ -1161,6 +1171,7 @@ int fasp_hip_bsr_solve(fasp_hip_amg_bsr* h, const dvector* b, dvector* x, const 
     t0 = wall_seconds();
     HIPCK(hipMemcpy(x->val + off0, h->u, sizeof(double) * n, hipMemcpyDeviceToHost));
     t_up += wall_seconds() - t0;
+    if (h->L[0].ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve of the cycle that timed out
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->iters = st; stats->nhist = H.n; stats->relres = po.relres; stats->absres = po.absres;
@@ -1440,6 +1451,7 @@ void fasp_hip_bsr_precond_fct(double* r, double* z, void* data)
     double* dz = nullptr;
     if (!dr.d || precond_amg_bsr(h, dr.d, &dz) < 0) die_bsr(__func__);
     (void)hipStreamSynchronize(g_ctx.stream);
+    if (h->L[0].ilu && seq_err_check() < 0) die_bsr(__func__);   // a single-launch ILU solve of the cycle that timed out
     (void)hipMemcpy(z, dz, sizeof(double) * n, hipMemcpyDeviceToHost);
 }
 
@@ -1532,7 +1544,7 @@ int krylov_plugin_bsr(const char* fn, int which, dBSRmat* A, dvector* b, dvector
         st = gmres_device(K, db.d, du.d, which == 2 ? 1 : which == 4 ? 3 : 0, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
     }
     du.get(u->val);
-    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
+    if ((ilu || (h && h->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
     for (double* q : ws) if (q) (void)hipFree(q);
     if (hh) (void)hipFree(hh);
     return st;
@@ -2228,6 +2240,7 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "split_rows")) g_tune.split_rows = value;
     else if (!std::strcmp(key, "gs_multicolor")) g_tune.gs_multicolor = value;
     else if (!std::strcmp(key, "seq_flow")) { g_tune.seq_flow = value; if (value) g_flow_disabled = false; }
+    else if (!std::strcmp(key, "ilu_smooth_fused")) g_tune.ilu_smooth_fused = value;   // ILU step of the block cycle: 1 (default) the U solve writes x = x + z itself, 0 a separate axpy pass -- same bits
     else if (!std::strcmp(key, "ilu_form")) g_tune.ilu_form = value;   // ILU triangular solves: -1 (default) by the schedule's depth, 0 one launch per level, 1 one launch
     else if (!std::strcmp(key, "seq_strip_kb")) g_tune.seq_strip_kb = value;   // KB of lower entries per strip of the dataflow solve (0, default: 256 / 512 / 1024 by level shape, seq_sched.cpp)
     else if (!std::strcmp(key, "seq_jobs")) g_tune.seq_jobs = value;

@@ -674,7 +674,10 @@ void fasp_smoother_dcsr_L1diag(dvector* u, const int i_1, const int i_n, const i
  * inverted), 1 <= nb <= 7; it needs no GPU.  fasp_precond_dbsr_ilu applies it with block triangular solves on the device
  * (bit for bit the reference's z; resident from the first application until fasp_ilu_data_free, as above), the block
  * Krylov methods recognise it and keep it in HBM; fasp_solver_dbsr_krylov_ilu = setup + fasp_solver_dbsr_itsolver.
- * ILU as an AMG smoother (ILU_levels > 0), structured ILU and Schwarz stay out of scope. */
+ * ILU as a smoother of the block AMG cycle: AMG_param.ILU_levels > 0 with fasp_solver_dbsr_krylov_amg, the fasp_hip_bsr_*
+ * handles and fasp_hip_bsr_precond_setup factors the levels below ILU_levels on the host (PreAMGSetupUABSR.c:149-179) and
+ * smooths them on the device with one ILU step + block Gauss-Seidel sweeps (PreMGCycle.c:321-326); one GPU only.  The
+ * scalar AMG cycle (fasp_solver_dcsr_krylov_amg with ILU_levels > 0), structured ILU and Schwarz stay out of scope. */
 void  fasp_param_ilu_init(ILU_param* iluparam);                                     /* AuxParam.c:595 */
 void  fasp_ilu_data_create(const int iwk, const int nwork, ILU_data* iludata);      /* PreDataInit.c:411 */
 void  fasp_ilu_data_free(ILU_data* iludata);                                        /* PreDataInit.c:445 */

@@ -49,6 +49,18 @@ int fasp_hip_measure_ceilings(double* out, size_t bytes, int reps);
  * is (the registry's record), its bytes counted from the block layout. */
 int    fasp_hip_ilu_resident_count(void);
 double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
+/* ILU smoothing in the block AMG cycle (AMG_param.ILU_levels > 0 with a BSR hierarchy).  The factors belong to the hierarchy:
+ * they are not among fasp_hip_ilu_resident_count's.  fasp_hip_bsr_amg_get_ilu: *view = the host factor of `level` (borrowed:
+ * valid until the hierarchy is destroyed, not to be freed); returns 1, or 0 when the level has none (at or beyond ILU_levels,
+ * the coarsest level, a failed factorisation), < 0 on bad arguments.  fasp_hip_bsr_amg_ilu_info: the schedule of the level's
+ * device copy, info = {dependency levels of L, of U, form of the L solve, of the U solve (1 single launch, 0 level launches, as
+ * fasp_hip_tune("ilu_form", ..) stands now), chunks of 64 rows of L, of U}; returns 1, or 0 (info zeroed) when the level has no
+ * device factor (host-only hierarchies have none).  fasp_hip_bsr_amg_ilu_smooth_time: microseconds per ILU smoothing step of
+ * the cycle on `level` (residual, L solve, U solve that also writes x = x + z) over `reps` back-to-back steps after one
+ * warm-up; fasp_hip_tune("ilu_smooth_fused", 0) times the form it replaced (the U solve, then a separate axpy); < 0: error. */
+int    fasp_hip_bsr_amg_get_ilu(const fasp_hip_amg_bsr* h, int level, ILU_data* view);
+int    fasp_hip_bsr_amg_ilu_info(const fasp_hip_amg_bsr* h, int level, double info[6]);
+double fasp_hip_bsr_amg_ilu_smooth_time(fasp_hip_amg_bsr* h, int level, int reps);
 
 /* Run-time switches (A/B tests, profiling, and ONE behavioural mode):
  *   kernel selection / launch geometry: maxgrid, xcd, nt, kind, lanes, wrows, wcap (-1 = automatic), gen2 (0 round-1
@@ -79,6 +91,8 @@ double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
  *     the reference's sequential sweep, reproduced exactly;
  *   ILU preconditioner: ilu_form (the triangular solves of fasp_precond_ilu and its kin: -1 (default) one launch for schedules
  *     deeper than 24 levels, else one launch per level; 0 always one launch per level; 1 always one launch) -- same bits;
+ *     ilu_smooth_fused (the ILU step of the block AMG cycle: 1 (default) the U solve writes x = x + z itself, 0 a separate
+ *     axpy pass) -- same bits;
  *   multi-GPU: halo_overlap (exchange beside the interior rows, default 1), split_rows (test mode: every operator in
  *     three row windows), seq_partition (set before the upload, or FASP_HIP_SEQ_PARTITION=1: hierarchies with Gauss-Seidel / SOR
  *     smoothers are row-partitioned too and the ranks sweep by turns; default 0: such hierarchies keep every level whole),

@@ -4,6 +4,12 @@ factor, one BSR SpMV of A (fasp_hip_time_bsr_mxv) and the scalar ILU(0) of P7(12
 for L + U).  Ends with one end-to-end fasp_solver_dbsr_krylov_ilu (BiCGstab, ILU(0)) at P7(128) (x) B3.
 
     python tools/perf_bilu.py [--cases 128:3:0,64:2:0,64:5:0,64:7:0,64:3:1] [--reps 20] [--out profiles/bilu_apply.txt]
+
+--smoother times the ILU smoothing step of the block AMG cycle instead (AMG_param.ILU_levels = 1, level 0 of P7(64) (x) B3,
+ILU(0)): the step whose U solve writes x = x + z itself against the three passes it replaces (residual, both solves, axpy),
+the two forms alternating in one run on one resident hierarchy.
+
+    python tools/perf_bilu.py --smoother [--n 64] [--reps 20] [--rounds 5] [--out profiles/bilu_smoother.txt]
 """
 import argparse
 import ctypes as C
@@ -31,6 +37,36 @@ def block_of(nb):
     return np.diag(np.full(nb, 4.0)) + np.diag(np.ones(nb - 1), 1) + np.diag(np.ones(nb - 1), -1)
 
 
+def smoother_leg(args, L, out):
+    n, nb = args.n, 3
+    ia, ja, val, _ = _libs.poisson7pt_bsr(n)
+    amgp = fa.param_amg_init()
+    amgp.AMG_type, amgp.aggregation_type, amgp.smoother = T.UA_AMG, 2, T.SMOOTHER_JACOBI
+    amgp.ILU_levels, amgp.ILU_lfil = 1, 0
+    G = fa.BSRAMG(ia, ja, val, nb, amgp)
+    info = G.ilu_info(0)
+    out(f"\nILU smoothing step of the block cycle, level 0 of P7({n}) (x) B{nb}, ILU(0): {n ** 3} block rows, {G.num_levels} levels, "
+        f"L / U {info[0]} / {info[1]} dependency levels, {'single launch' if info[3] else 'level launches'}")
+    t = {1: [], 0: []}
+    try:
+        for rnd in range(args.rounds):   # the forms alternate: drifts of the machine hit both alike
+            for fused in (1, 0):
+                L.fasp_hip_tune(b"ilu_smooth_fused", fused)
+                us = G.ilu_smooth_time(0, args.reps)
+                assert us > 0
+                t[fused].append(us)
+    finally:
+        L.fasp_hip_tune(b"ilu_smooth_fused", 1)
+        G.free()
+    for fused, name in ((1, "fused (U solve writes x = x + z)"), (0, "three calls (residual, both solves, axpy)")):
+        v = np.array(t[fused])
+        out(f"  {name:44s}: median {np.median(v):9.1f} us per step, min {v.min():9.1f}, max {v.max():9.1f}  ({args.rounds} rounds x {args.reps} steps)")
+    m1, m0 = np.median(t[1]), np.median(t[0])
+    out(f"  fused / three calls = {m1 / m0:.4f} ({m0 - m1:+.1f} us saved per step; one vector pass over {n ** 3 * nb} doubles read twice and "
+        f"written once = {24.0 * n ** 3 * nb / 1e6:.1f} MB)")
+    out("  the cycle uses the " + ("fused form" if m1 <= m0 else "THREE-CALL form would be faster here: see fasp_hip_tune(\"ilu_smooth_fused\", 0)"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="128:3:0,64:2:0,64:5:0,64:7:0,64:3:1", help="n:nb:lfil of ILUk on P7(n) (x) B_nb")
@@ -38,6 +74,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-ref", action="store_true", help="skip the reference's CPU application")
     ap.add_argument("--no-solve", action="store_true", help="skip the end-to-end solve")
+    ap.add_argument("--smoother", action="store_true", help="time the ILU smoothing step of the block AMG cycle instead")
+    ap.add_argument("--n", type=int, default=64, help="--smoother: P7(n) (x) B3")
+    ap.add_argument("--rounds", type=int, default=5, help="--smoother: alternations of the two forms")
     args = ap.parse_args()
     L = fa.lib()
     if not fa.available():
@@ -54,7 +93,10 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    for case in args.cases.split(","):
+    if args.smoother:
+        smoother_leg(args, L, out)
+        args.cases, args.no_solve = "", True
+    for case in filter(None, args.cases.split(",")):
         n, nb, lfil = (int(v) for v in case.split(":"))
         ia, ja, val, _ = _libs.poisson7pt_bsr(n, block_of(nb))
         A, keep = T.as_bsr(ia, ja, val, nb)
