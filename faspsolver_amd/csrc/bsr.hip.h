@@ -85,9 +85,7 @@ struct fasp_hip_amg_bsr {
     DistPlan              dist;
     bool                  distributed = false;   // level 0 is row-partitioned over the ranks
     double *b = nullptr, *u = nullptr, *p = nullptr, *t = nullptr, *r = nullptr, *z = nullptr;
-    std::vector<double*> gm[2];
-    size_t               gm_len[2] = {0, 0};
-    double*              gm_hh = nullptr;
+    KrylovWs             gm[2];   // Krylov workspaces: level-0 set and coarse-level set
     double*              small_ws = nullptr;  // workspace of the single-workgroup coarse GMRES
     long long            coarse_iters = 0, vcycles = 0;
     int                  coarse_kinfo[6] = {0, 0, 0, 0, 0, 0};   // the last coarse solve (fasp_hip_bsr_coarse_kernel_info)
@@ -365,7 +363,7 @@ static KOps bsr_ops(fasp_hip_amg_bsr* h, int level, int set)
     K.mxv = [Lv](const double* x, double* y) { bsr_mxv(*Lv->A, x, y); };
     K.resid = [Lv](const double* x, const double* b, double* r) { bsr_resid(*Lv->A, x, b, r); };
     if (set == 0) K.pc = [h](double* in, double** out) { return precond_amg_bsr(h, in, out); };
-    K.ws = &h->gm[set]; K.ws_len = &h->gm_len[set]; K.hh = &h->gm_hh;
+    K.ws = &h->gm[set];
     K.stats = nullptr;
     return K;
 }

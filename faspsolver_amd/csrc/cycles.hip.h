@@ -553,7 +553,7 @@ static KOps csr_ops(fasp_hip_amg* h, int level, bool with_pc)
         };
     }
     const int set = level == 0 ? 0 : 1;
-    K.ws = &h->gm[set]; K.ws_len = &h->gm_len[set]; K.hh = &h->gm_hh;
+    K.ws = &h->gm[set];
     K.stats = h;
     return K;
 }

@@ -61,6 +61,14 @@ struct DevLevel {
 
 struct EventPair { hipEvent_t a, b; };
 
+// the Krylov workspace (krylov_ws.h) on the device: vectors zeroed on the solver's stream
+struct HipWsMem {
+    static int  alloc(double** q, size_t n) { HIPCK(hipMalloc(q, sizeof(double) * std::max<size_t>(n, 1))); return 0; }
+    static int  zero(double* q, size_t n) { HIPCK(hipMemsetAsync(q, 0, sizeof(double) * n, g_ctx.stream)); return 0; }
+    static void release(double* q) { (void)hipFree(q); }
+};
+using KrylovWs = KrylovWsT<HipWsMem>;
+
 }  // namespace fasp
 
 using namespace fasp;
@@ -88,10 +96,8 @@ struct fasp_hip_amg {
     double *b = nullptr, *u = nullptr, *p = nullptr, *t = nullptr, *r = nullptr;
     // coarse-level SPCG work vectors
     double *cp = nullptr, *cr = nullptr, *ct = nullptr, *cbest = nullptr;
-    // GMRES basis vectors (allocated on first use): level-0 set and coarse-level set
-    std::vector<double*> gm[2];
-    size_t               gm_len[2] = {0, 0};
-    double*              gm_hh = nullptr;  // device Hessenberg column
+    // Krylov workspaces (allocated on first use): level-0 set and coarse-level set, each with its own Hessenberg column
+    KrylovWs             gm[2];
     double*              spcg_fused_buf = nullptr;  // second parity of r, p, t and the broadcast record (k_spcg_fused)
     int                  spcg_last_iters = 0;   // iterations of the previous coarse solve: sizes the first batch of the next one
     SpcgState*           spcg_state = nullptr;  // device-resident state of the batched coarse CG

@@ -448,10 +448,11 @@ IluDev* ilu_of_precond(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluD
     return ilu_device_of(d, false, tmp, st);
 }
 
-// the same for the block Krylov plug-in: fasp_precond_dbsr_ilu, n = block rows * nb of the system
-IluDev* ilu_of_precond_bsr(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* st)
+// the same for the block Krylov plug-in: fasp_precond_dbsr_ilu (*which = 0), n = block rows * nb of the system
+IluDev* ilu_of_precond_bsr(precond* pc, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>& tmp, int* which, int* st)
 {
     *st = FASP_SUCCESS;
+    *which = 0;
     if (!pc || !pc->data || pc->fct != fasp_precond_dbsr_ilu) return nullptr;
     IluDev* D = ilu_device_of(static_cast<ILU_data*>(pc->data), true, tmp, st);
     if (D && D->n * D->nb != n) { *st = ERROR_INPUT_PAR; return nullptr; }

@@ -1,4 +1,5 @@
 // krylov.hip.h -- Krylov drivers on device vectors against the operator bundle KOps: GMRES family, BiCGstab, MinRes, GCG, GCR, matrix-free texts.
+// Their work vectors come from the KrylovWs the bundle points to (krylov_ws.h: it owns them); krylov_run (pcg.hip.h) maps a method to its driver.
 // Part of the single translation unit solver.hip (included there, in this order; not a stand-alone header).
 
 struct KOps;
@@ -34,11 +35,11 @@ struct KOps {
     double pre_omega = 0.0;
     std::function<void()> mark_presmoothed;
     std::function<int(double*, double**, int*)> pc_zr;                     // pc + partials of (out, in) in g_ctx.d_partials (count in *G, 0: none)
-    std::vector<double*>* ws = nullptr;                                    // GMRES workspace
-    size_t* ws_len = nullptr;
-    double** hh = nullptr;
+    KrylovWs* ws = nullptr;                                                // work vectors and Hessenberg column (owned by a handle or by the plug-in driver)
     fasp_hip_amg* stats = nullptr;                                         // event pool for the SpMV timer
 };
+
+#define KCK(expr) do { const int st__ = (expr); if (st__ < 0) return st__; } while (0)
 
 static void d_scale(int n, double a, double* x)
 {
@@ -81,21 +82,11 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
 
     // workspace: p[0..Restart], w, x_best (mode 2), z[0..Restart) (mode 1)
     const size_t need = (size_t)Restart1 + 2 + (mode == 1 ? (size_t)Restart1 : 0);
-    if (*K.ws_len != nv) {
-        for (double* q : *K.ws) if (q) (void)hipFree(q);
-        K.ws->clear();
-        *K.ws_len = nv;
-    }
-    while (K.ws->size() < need) {
-        double* q = nullptr;
-        HIPCK(hipMalloc(&q, sizeof(double) * std::max<size_t>(nv, 1)));
-        HIPCK(hipMemsetAsync(q, 0, sizeof(double) * nv, s));
-        K.ws->push_back(q);
-    }
-    if (!*K.hh) HIPCK(hipMalloc(K.hh, sizeof(double) * 1024));
-    if (Restart1 + 2 > 1024) return ERROR_INPUT_PAR;
-    std::vector<double*>& W = *K.ws;
-    double* const gm_hh = *K.hh;
+    KCK(K.ws->ensure(need, nv));
+    double* const gm_hh = K.ws->hessenberg();
+    if (!gm_hh) return ERROR_MISC;
+    if (Restart1 + 2 > (int)KrylovWs::HH_LEN) return ERROR_INPUT_PAR;
+    KrylovWs& W = *K.ws;
     double** p = W.data();
     double*  w = W[Restart1];
     double*  x_best = W[Restart1 + 1];
@@ -368,18 +359,8 @@ static int bicgstab_device(KOps& K, const double* b, double* x, double tol, int 
     const size_t nv = K.nvec;
     const bool dist = K.dist;
     hipStream_t s = g_ctx.stream;
-    if (*K.ws_len != nv) {
-        for (double* q : *K.ws) if (q) (void)hipFree(q);
-        K.ws->clear();
-        *K.ws_len = nv;
-    }
-    while (K.ws->size() < 9) {
-        double* q = nullptr;
-        HIPCK(hipMalloc(&q, sizeof(double) * std::max<size_t>(nv, 1)));
-        HIPCK(hipMemsetAsync(q, 0, sizeof(double) * nv, s));
-        K.ws->push_back(q);
-    }
-    std::vector<double*>& W = *K.ws;
+    KCK(K.ws->ensure(9, nv));
+    KrylovWs& W = *K.ws;
     double *r = W[0], *rt = W[1], *p = W[2], *v = W[3], *xhalf = W[4], *sv = W[5], *t = W[6], *xmin = W[7], *tmp = W[8];
     double *ph = nullptr, *sh = nullptr;  // preconditioned vectors (may alias the preconditioner's output)
     double red[8];
@@ -541,21 +522,7 @@ struct KVecOps {
     hipStream_t s;
     double red[8];
     explicit KVecOps(KOps& K_) : K(K_), m(K_.n), nv(K_.nvec), s(g_ctx.stream) {}
-    int ensure(size_t count)
-    {
-        if (*K.ws_len != nv) {
-            for (double* q : *K.ws) if (q) (void)hipFree(q);
-            K.ws->clear();
-            *K.ws_len = nv;
-        }
-        while (K.ws->size() < count) {
-            double* q = nullptr;
-            HIPCK(hipMalloc(&q, sizeof(double) * std::max<size_t>(nv, 1)));
-            HIPCK(hipMemsetAsync(q, 0, sizeof(double) * nv, s));
-            K.ws->push_back(q);
-        }
-        return 0;
-    }
+    int ensure(size_t count) { return K.ws->ensure(count, nv); }
     double* vec(size_t i) { return (*K.ws)[i]; }
     int cp(double* dst, const double* src)
     {
@@ -594,7 +561,51 @@ struct KVecOps {
         return cp(dst, o);
     }
 };
-#define KCK(expr) do { const int st__ = (expr); if (st__ < 0) return st__; } while (0)
+
+// The two blocks minres_device and minres_mf_device share word for word (the reference's two MinRes texts agree there):
+// the start of the Lanczos recurrence and one step of it, on the vectors both texts name alike.
+struct MinresVecs { double *p0, *p1, *p2, *z0, *z1, *t0, *t1, *t, *tp, *tz, *r; };
+static int minres_lanczos_start(KVecOps& V, const MinresVecs& W)  // p1 = B r on entry: p1, t1 = A p1, z1 = B t1, normalised
+{
+    double normp;
+    KCK(V.mxv(W.p1, W.tp));
+    KCK(V.pc(W.tp, W.tz));
+    KCK(V.dot(W.tz, W.tp, normp));
+    normp = std::sqrt(std::fabs(normp));
+    KCK(V.cp(W.t, W.p1));
+    KCK(V.zero(W.p1));
+    d_axpy(V.m, 1 / normp, W.t, W.p1);
+    KCK(V.zero(W.t0)); KCK(V.zero(W.z0)); KCK(V.zero(W.t1)); KCK(V.zero(W.z1));
+    d_axpy(V.m, 1.0 / normp, W.tp, W.t1);
+    d_axpy(V.m, 1.0 / normp, W.tz, W.z1);
+    return 0;
+}
+static int minres_lanczos_step(KVecOps& V, const MinresVecs& W, double* u, double& alpha)  // u, r updated; the next p, t, z
+{
+    double alpha0, alpha1, normp;
+    KCK(V.dot(W.r, W.z1, alpha));
+    d_axpy(V.m, alpha, W.p1, u);
+    d_axpy(V.m, -alpha, W.t1, W.r);
+    KCK(V.mxv(W.z1, W.t));
+    KCK(V.dot(W.z1, W.t, alpha1));
+    KCK(V.mxv(W.z0, W.t));
+    KCK(V.dot(W.z1, W.t, alpha0));
+    KCK(V.cp(W.p2, W.z1));
+    d_axpy(V.m, -alpha1, W.p1, W.p2);
+    d_axpy(V.m, -alpha0, W.p0, W.p2);
+    KCK(V.mxv(W.p2, W.tp));
+    KCK(V.pc(W.tp, W.tz));
+    KCK(V.dot(W.tz, W.tp, normp));
+    normp = std::sqrt(std::fabs(normp));
+    KCK(V.cp(W.t, W.p2));
+    KCK(V.zero(W.p2));
+    d_axpy(V.m, 1 / normp, W.t, W.p2);
+    KCK(V.cp(W.p0, W.p1)); KCK(V.cp(W.p1, W.p2)); KCK(V.cp(W.t0, W.t1)); KCK(V.cp(W.z0, W.z1));
+    KCK(V.zero(W.t1)); KCK(V.zero(W.z1));
+    d_axpy(V.m, 1 / normp, W.tp, W.t1);
+    d_axpy(V.m, 1 / normp, W.tz, W.z1);
+    return 0;
+}
 
 // fasp_solver_dcsr_pminres, KryPminres.c:61-448
 static int minres_device(KOps& K, const double* b, double* u, double tol, double abstol, int MaxIt, int StopType,
@@ -605,10 +616,11 @@ static int minres_device(KOps& K, const double* b, double* u, double tol, double
     const double maxdiff = tol * STAG_RATIO, sol_inf_tol = SMALLREAL;
     int iter = 0, stag = 1, more_step = 1;
     double absres0 = BIGREAL, absres = BIGREAL, normr0 = BIGREAL, relres = BIGREAL;
-    double normu2 = BIGREAL, normuu, normp, factor, alpha, alpha0, alpha1, temp2, red[8];
+    double normu2 = BIGREAL, normuu, normp, factor, alpha, temp2, red[8];
     KCK(V.ensure(11));
     double *p0 = V.vec(0), *p1 = V.vec(1), *p2 = V.vec(2), *z0 = V.vec(3), *z1 = V.vec(4), *t0 = V.vec(5),
            *t1 = V.vec(6), *t = V.vec(7), *tp = V.vec(8), *tz = V.vec(9), *r = V.vec(10);
+    const MinresVecs W{p0, p1, p2, z0, z1, t0, t1, t, tp, tz, r};
     auto resnorm = [&]() -> int {  // :228-247 and its two copies
         switch (StopType) {
             case STOP_REL_RES:
@@ -655,39 +667,10 @@ static int minres_device(KOps& K, const double* b, double* u, double tol, double
     if (hist) hist->push(absres0);
     if (relres < tol || absres0 < abstol) goto FINISHED;
     itinfo(PrtLvl, StopType, iter, relres, absres0, 0.0);
-    KCK(V.mxv(p1, tp));
-    KCK(V.pc(tp, tz));
-    KCK(V.dot(tz, tp, normp));
-    normp = std::sqrt(std::fabs(normp));
-    KCK(V.cp(t, p1));
-    KCK(V.zero(p1));
-    d_axpy(m, 1 / normp, t, p1);
-    KCK(V.zero(t0)); KCK(V.zero(z0)); KCK(V.zero(t1)); KCK(V.zero(z1));
-    d_axpy(m, 1.0 / normp, tp, t1);
-    d_axpy(m, 1.0 / normp, tz, z1);
+    KCK(minres_lanczos_start(V, W));
 
     while (iter++ < MaxIt) {
-        KCK(V.dot(r, z1, alpha));
-        d_axpy(m, alpha, p1, u);
-        d_axpy(m, -alpha, t1, r);
-        KCK(V.mxv(z1, t));
-        KCK(V.dot(z1, t, alpha1));
-        KCK(V.mxv(z0, t));
-        KCK(V.dot(z1, t, alpha0));
-        KCK(V.cp(p2, z1));
-        d_axpy(m, -alpha1, p1, p2);
-        d_axpy(m, -alpha0, p0, p2);
-        KCK(V.mxv(p2, tp));
-        KCK(V.pc(tp, tz));
-        KCK(V.dot(tz, tp, normp));
-        normp = std::sqrt(std::fabs(normp));
-        KCK(V.cp(t, p2));
-        KCK(V.zero(p2));
-        d_axpy(m, 1 / normp, t, p2);
-        KCK(V.cp(p0, p1)); KCK(V.cp(p1, p2)); KCK(V.cp(t0, t1)); KCK(V.cp(z0, z1));
-        KCK(V.zero(t1)); KCK(V.zero(z1));
-        d_axpy(m, 1 / normp, tp, t1);
-        d_axpy(m, 1 / normp, tz, z1);
+        KCK(minres_lanczos_step(V, W, u, alpha));
         if (d_norms(m, u, red, K.dist) < 0) return ERROR_MISC;  // ||u||^2, max|u|
         normu2 = std::sqrt(red[0]);
         KCK(resnorm());
@@ -764,10 +747,11 @@ static int minres_mf_device(KOps& K, const double* b, double* u, double tol, dou
     const double maxdiff = tol * STAG_RATIO, sol_inf_tol = SMALLREAL;
     int iter = 0, stag = 1, more_step = 1;
     double absres0 = BIGREAL, absres = BIGREAL, normr0 = BIGREAL, relres = BIGREAL;
-    double normu2 = BIGREAL, normuu, normp, factor, alpha, alpha0, alpha1, temp2, red[8];
+    double normu2 = BIGREAL, normuu, normp, factor, alpha, temp2, red[8];
     KCK(V.ensure(11));
     double *p0 = V.vec(0), *p1 = V.vec(1), *p2 = V.vec(2), *z0 = V.vec(3), *z1 = V.vec(4), *t0 = V.vec(5),
            *t1 = V.vec(6), *t = V.vec(7), *tp = V.vec(8), *tz = V.vec(9), *r = V.vec(10);
+    const MinresVecs W{p0, p1, p2, z0, z1, t0, t1, t, tp, tz, r};
     auto recheck = [&]() -> int {  // :1476-1497 == :1553-1573 (no default case)
         KCK(V.resid(u, b, r));
         KCK(V.dot(r, r, temp2));
@@ -810,39 +794,10 @@ static int minres_mf_device(KOps& K, const double* b, double* u, double tol, dou
             KCK(V.nrm2(r, absres0)); normr0 = std::max(SMALLREAL, absres0); relres = absres0 / normr0; break;
     }
     if (relres < tol || absres0 < abstol) goto FINISHED;
-    KCK(V.mxv(p1, tp));
-    KCK(V.pc(tp, tz));
-    KCK(V.dot(tz, tp, normp));
-    normp = std::sqrt(std::fabs(normp));
-    KCK(V.cp(t, p1));
-    KCK(V.zero(p1));
-    d_axpy(m, 1 / normp, t, p1);
-    KCK(V.zero(t0)); KCK(V.zero(z0)); KCK(V.zero(t1)); KCK(V.zero(z1));
-    d_axpy(m, 1.0 / normp, tp, t1);
-    d_axpy(m, 1.0 / normp, tz, z1);
+    KCK(minres_lanczos_start(V, W));
 
     while (iter++ < MaxIt) {
-        KCK(V.dot(r, z1, alpha));
-        d_axpy(m, alpha, p1, u);
-        d_axpy(m, -alpha, t1, r);
-        KCK(V.mxv(z1, t));
-        KCK(V.dot(z1, t, alpha1));
-        KCK(V.mxv(z0, t));
-        KCK(V.dot(z1, t, alpha0));
-        KCK(V.cp(p2, z1));
-        d_axpy(m, -alpha1, p1, p2);
-        d_axpy(m, -alpha0, p0, p2);
-        KCK(V.mxv(p2, tp));
-        KCK(V.pc(tp, tz));
-        KCK(V.dot(tz, tp, normp));
-        normp = std::sqrt(std::fabs(normp));
-        KCK(V.cp(t, p2));
-        KCK(V.zero(p2));
-        d_axpy(m, 1 / normp, t, p2);
-        KCK(V.cp(p0, p1)); KCK(V.cp(p1, p2)); KCK(V.cp(t0, t1)); KCK(V.cp(z0, z1));
-        KCK(V.zero(t1)); KCK(V.zero(z1));
-        d_axpy(m, 1 / normp, tp, t1);
-        d_axpy(m, 1 / normp, tz, z1);
+        KCK(minres_lanczos_step(V, W, u, alpha));
         KCK(V.dot(r, r, temp2));
         absres = std::sqrt(temp2);
         if (d_norms(m, u, red, K.dist) < 0) return ERROR_MISC;  // ||u||^2, max|u|

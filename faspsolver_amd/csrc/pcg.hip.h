@@ -283,3 +283,50 @@ static int cg_smooth(fasp_hip_amg* h, int level, int nsweeps)
     return (st == ERROR_MISC || st == ERROR_ALLOC_MEM) ? st : FASP_SUCCESS;
 }
 
+// ---------------------------------------------------------------------------
+// One dispatch on the method for every caller of the Krylov drivers: the resident entries (SolCSR.c:84-130,
+// SolBSR.c:55-150) and the plug-in level (solver.hip, krylov_plugin).
+// ---------------------------------------------------------------------------
+enum KMethod { K_CG = SOLVER_CG, K_BiCGstab = SOLVER_BiCGstab, K_MinRes = SOLVER_MinRes, K_GMRES = SOLVER_GMRES,
+               K_VGMRES = SOLVER_VGMRES, K_VFGMRES = SOLVER_VFGMRES, K_GCG = SOLVER_GCG, K_GCR = SOLVER_GCR };
+constexpr unsigned kbit(int m) { return (m >= K_CG && m <= K_GCR) ? 1u << m : 0u; }
+// the methods a family of entry points offers
+constexpr unsigned K_OFFER_BSR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_VFGMRES);
+constexpr unsigned K_OFFER_MATFREE = K_OFFER_BSR | kbit(K_MinRes) | kbit(K_GCG);
+constexpr unsigned K_OFFER_ALL = K_OFFER_MATFREE | kbit(K_GCR);
+struct KParams { double tol, abstol; int MaxIt, restart, StopType, PrtLvl; };
+
+// mf_texts: the reference's older texts for mxv_matfree (CG, MinRes and the GMRES variants; they keep no residual history);
+// p, t, r: scratch vectors of CG (unused by the other methods).  A method outside `offered`: ERROR_SOLVER_TYPE.
+static int krylov_run(KOps& K, KMethod method, unsigned offered, bool mf_texts, const KParams& P, const double* b, double* u,
+                      double* p, double* t, double* r, Hist* hist, PcgOut* out)
+{
+    if (!(offered & kbit(method))) return ERROR_SOLVER_TYPE;
+    const bool gm = method == K_GMRES || method == K_VGMRES || method == K_VFGMRES;
+    if (mf_texts && method == K_CG) return pcg_mf_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, out);
+    if (mf_texts && method == K_MinRes) return minres_mf_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, out);
+    if (mf_texts && gm)
+        return gmres_mf_device(K, method != K_GMRES, method == K_VFGMRES, b, u, P.tol, P.MaxIt, P.restart, P.StopType, P.PrtLvl, out);
+    switch (method) {
+        case K_CG: return pcg_device(K, PcgVecs{b, u, p, t, r}, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, *hist, *out);
+        case K_BiCGstab: return bicgstab_device(K, b, u, P.tol, P.MaxIt, P.PrtLvl, hist, out);
+        case K_MinRes: return minres_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, hist, out);
+        case K_GCG: return gcg_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, hist, out);
+        case K_GCR: return gcr_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.restart, P.StopType, P.PrtLvl, hist, out);
+        default:   // GMRES (fixed restart: mode 3), VGMRES (mode 0), VFGMRES (mode 1)
+            return gmres_device(K, b, u, method == K_VFGMRES ? 1 : method == K_GMRES ? 3 : 0, P.tol, P.abstol, P.MaxIt, P.restart,
+                                P.StopType, P.PrtLvl, hist, out);
+    }
+}
+
+// ITS_CHECK, KryUtil.inl:71-83, and the timing line of the *_itsolver dispatchers
+static void its_check(double tol, int MaxIt)
+{
+    if (tol < SMALLREAL) std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
+    if (MaxIt <= 0) std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+}
+static void print_itsolver_time(int PrtLvl, int iter, double seconds)
+{
+    if (PrtLvl >= PRINT_SOME && iter >= 0) std::printf("Iterative method costs %.4f seconds.\n", seconds);
+}
+

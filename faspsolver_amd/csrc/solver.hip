@@ -39,6 +39,7 @@
 
 #include "fasp_comm.h"
 #include "fasp_internal.h"
+#include "krylov_ws.h"
 #include "kernels.hip.h"
 #include "kernels2.hip.h"
 #include "kernels3.hip.h"
@@ -494,10 +495,6 @@ void fasp_hip_amg_destroy(fasp_hip_amg* h)
     if (h->reg_img) (void)hipFree(h->reg_img);
     if (h->h_lazy) (void)hipHostFree(h->h_lazy);
     for (auto& e : h->ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (int s = 0; s < 2; ++s)
-        for (double* q : h->gm[s])
-            if (q) (void)hipFree(q);
-    if (h->gm_hh) (void)hipFree(h->gm_hh);
     if (h->spcg_state) (void)hipFree(h->spcg_state);
     if (h->spcg_fused_buf) (void)hipFree(h->spcg_fused_buf);
     {
@@ -687,11 +684,7 @@ int fasp_hip_solve_resident(fasp_hip_amg* h, const ITS_param* itparam, double* h
     if (h->L.empty()) return ERROR_INPUT_PAR;  // hierarchy not uploaded
     int st = check_supported(itparam, &h->param);
     if (st < 0) return st;
-    // ITS_CHECK, KryUtil.inl:71-83
-    if (itparam->tol < SMALLREAL)
-        std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
-    if (itparam->maxit <= 0)
-        std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+    its_check(itparam->tol, itparam->maxit);
 
     h->ev_used = 0;
     h->use_fmg = itparam->precond_type == PREC_FMG;   // SolCSR.c:537-538
@@ -700,47 +693,11 @@ int fasp_hip_solve_resident(fasp_hip_amg* h, const ITS_param* itparam, double* h
     PcgOut po{BIGREAL, BIGREAL, BIGREAL};
     const double t0 = wall_seconds();
     // SolCSR.c:530-551: the AMG preconditioner is always installed on this path;
-    // SolCSR.c:84-130: dispatch on itsolver_type (restart is narrowed to SHORT, :62)
-    switch (itparam->itsolver_type) {
-        case SOLVER_BiCGstab:
-        {
-            KOps K = csr_ops(h, 0, true);
-            st = bicgstab_device(K, h->b, h->u, itparam->tol, itparam->maxit, itparam->print_level, &H, &po);
-        } break;
-        case SOLVER_GMRES:
-        case SOLVER_VGMRES:
-        case SOLVER_VFGMRES:
-        {
-            KOps K = csr_ops(h, 0, true);
-            st = gmres_device(K, h->b, h->u, itparam->itsolver_type == SOLVER_VFGMRES ? 1 : itparam->itsolver_type == SOLVER_GMRES ? 3 : 0, itparam->tol,
-                              itparam->abstol, itparam->maxit, (short)itparam->restart, itparam->stop_type,
-                              itparam->print_level, &H, &po);
-        } break;
-        case SOLVER_MinRes:
-        {
-            KOps K = csr_ops(h, 0, true);
-            st = minres_device(K, h->b, h->u, itparam->tol, itparam->abstol, itparam->maxit, itparam->stop_type,
-                               itparam->print_level, &H, &po);
-        } break;
-        case SOLVER_GCG:
-        {
-            KOps K = csr_ops(h, 0, true);
-            st = gcg_device(K, h->b, h->u, itparam->tol, itparam->abstol, itparam->maxit, itparam->stop_type,
-                            itparam->print_level, &H, &po);
-        } break;
-        case SOLVER_GCR:
-        {
-            KOps K = csr_ops(h, 0, true);
-            st = gcr_device(K, h->b, h->u, itparam->tol, itparam->abstol, itparam->maxit, (short)itparam->restart,
-                            itparam->stop_type, itparam->print_level, &H, &po);
-        } break;
-        default:
-        {
-            KOps K = csr_ops(h, 0, true);
-            PcgVecs V{h->b, h->u, h->p, h->t, h->r};
-            st = pcg_device(K, V, itparam->tol, itparam->abstol, itparam->maxit, itparam->stop_type,
-                            itparam->print_level, H, po);
-        }
+    // SolCSR.c:84-130: dispatch on itsolver_type (restart is narrowed to SHORT, :62); check_supported let only known types pass
+    {
+        KOps K = csr_ops(h, 0, true);
+        const KParams P{itparam->tol, itparam->abstol, itparam->maxit, (short)itparam->restart, itparam->stop_type, itparam->print_level};
+        st = krylov_run(K, (KMethod)itparam->itsolver_type, K_OFFER_ALL, false, P, h->b, h->u, h->p, h->t, h->r, &H, &po);
     }
     HIPCK(hipStreamSynchronize(g_ctx.stream));
     if (seq_err_check() < 0) return ERROR_MISC;   // a broken cluster of the sequential smoothers (smoothers.hip.h)
@@ -759,8 +716,7 @@ int fasp_hip_solve_resident(fasp_hip_amg* h, const ITS_param* itparam, double* h
         stats->coarse_iters = h->coarse_iters - ci0;
         stats->vcycles = h->vcycles - vc0;
     }
-    if (itparam->print_level >= PRINT_SOME && st >= 0)
-        std::printf("Iterative method costs %.4f seconds.\n", t_solve);
+    print_itsolver_time(itparam->print_level, st, t_solve);
     return st;
 }
 
@@ -982,9 +938,6 @@ void fasp_hip_bsr_amg_destroy(fasp_hip_amg_bsr* h)
     }
     double* v[] = {h->b, h->u, h->p, h->t, h->r};
     for (double* q : v) if (q) (void)hipFree(q);
-    for (int s = 0; s < 2; ++s)
-        for (double* q : h->gm[s]) if (q) (void)hipFree(q);
-    if (h->gm_hh) (void)hipFree(h->gm_hh);
     if (h->small_ws) (void)hipFree(h->small_ws);
     delete h;
 }
@@ -1132,10 +1085,7 @@ int fasp_hip_bsr_solve(fasp_hip_amg_bsr* h, const dvector* b, dvector* x, const 
     if (b->row != nglob || x->row != nglob) return ERROR_MAT_SIZE;
     int st = check_supported_bsr(itparam, &h->param, h->H.L[0].A.nb);
     if (st < 0) return st;
-    if (itparam->tol < SMALLREAL)
-        std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
-    if (itparam->maxit <= 0)
-        std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+    its_check(itparam->tol, itparam->maxit);
     hipStream_t s = g_ctx.stream;
     double t0 = wall_seconds();
     HIPCK(hipMemcpyAsync(h->b, b->val + off0, sizeof(double) * n, hipMemcpyHostToDevice, s));
@@ -1148,24 +1098,8 @@ int fasp_hip_bsr_solve(fasp_hip_amg_bsr* h, const dvector* b, dvector* x, const 
     PcgOut po{BIGREAL, BIGREAL, BIGREAL};
     t0 = wall_seconds();
     KOps K = bsr_ops(h, 0, 0);
-    switch (itparam->itsolver_type) {  // fasp_solver_dbsr_itsolver, SolBSR.c:55-150
-        case SOLVER_BiCGstab:
-            st = bicgstab_device(K, h->b, h->u, itparam->tol, itparam->maxit, itparam->print_level, &H, &po);
-            break;
-        case SOLVER_GMRES:
-        case SOLVER_VGMRES:
-        case SOLVER_VFGMRES:
-            st = gmres_device(K, h->b, h->u, itparam->itsolver_type == SOLVER_VFGMRES ? 1 : itparam->itsolver_type == SOLVER_GMRES ? 3 : 0, itparam->tol,
-                              itparam->abstol, itparam->maxit, (short)itparam->restart, itparam->stop_type,
-                              itparam->print_level, &H, &po);
-            break;
-        default:
-        {
-            PcgVecs V{h->b, h->u, h->p, h->t, h->r};
-            st = pcg_device(K, V, itparam->tol, itparam->abstol, itparam->maxit, itparam->stop_type,
-                            itparam->print_level, H, po);
-        }
-    }
+    const KParams P{itparam->tol, itparam->abstol, itparam->maxit, (short)itparam->restart, itparam->stop_type, itparam->print_level};
+    st = krylov_run(K, (KMethod)itparam->itsolver_type, K_OFFER_BSR, false, P, h->b, h->u, h->p, h->t, h->r, &H, &po);   // fasp_solver_dbsr_itsolver, SolBSR.c:55-150
     HIPCK(hipStreamSynchronize(s));
     const double t_solve = wall_seconds() - t0;
     t0 = wall_seconds();
@@ -1179,8 +1113,7 @@ int fasp_hip_bsr_solve(fasp_hip_amg_bsr* h, const dvector* b, dvector* x, const 
         stats->coarse_iters = h->coarse_iters - ci0;
         stats->vcycles = h->vcycles - vc0;
     }
-    if (itparam->print_level >= PRINT_SOME && st >= 0)
-        std::printf("Iterative method costs %.4f seconds.\n", t_solve);
+    print_itsolver_time(itparam->print_level, st, t_solve);
     return st;
 }
 
@@ -1289,95 +1222,219 @@ bool same_host_matrix(const HostCSR& M, const dCSRmat* A)
            std::memcmp(M.val.data(), A->val, sizeof(double) * (size_t)A->nnz) == 0;
 }
 
-// which: 0 PCG, 1 VGMRES, 2 VFGMRES, 3 BiCGstab, 4 GMRES (fixed restart), 5 MinRes, 6 GCG, 7 GCR
-int krylov_plugin(const char* fn, int which, dCSRmat* A, dvector* b, dvector* u, precond* pc, double tol,
-                  double abstol, int MaxIt, short restart, short StopType, short PrtLvl)
+// ---------------------------------------------------------------------------
+// The plug-in driver: every Krylov entry point with a caller's `precond` -- CSR (SolCSR.c), BSR (SolBSR.c) and
+// matrix-free (SolMatFree.c) -- is this one function.  What the three families do differently is a KFamily.
+// ---------------------------------------------------------------------------
+struct PcState;
+// Each field mirrors what the family's own function did before the three were merged; none of them is a choice made here.
+struct KFamily {
+    const char* fmt;             // K.fmt, the "(%s)" of the solvers' first line: "CSR" / "BSR" / "MatFree", as today
+    bool ctx_first;              // ctx_init() before the argument checks, failure -> die_no_device (BSR: after them, via TmpBSR)
+    bool bad_bsr_dies;           // a BSR operator that cannot be uploaded -> die_bsr (matrix-free: ERROR_ALLOC_MEM), as today
+    bool refuse_multi_rank;      // comm_size() > 1 -> ERROR_INPUT_PAR; the BSR family has never checked
+    bool refuse_empty;           // b->row <= 0 -> ERROR_INPUT_PAR; only the matrix-free family checks, as today
+    int  (*find_amg)(precond*, int n, PcState&);   // which `precond`s are a device AMG handle; < 0: one of another size
+    bool borrow_resident;        // same_host_matrix: solve on the handle's resident level-0 operator (CSR only, as today)
+    bool fused_mxv_dot;          // K.mxv_dot for a CSR operator (CSR only; the matrix-free texts never ask for it)
+    bool (*bind_diag)(precond*, int n, int nb, PcState&, KOps&, int* st);   // (block-)diagonal preconditioner on the device; none: host-staged
+    IluDev* (*ilu_lookup)(precond*, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>&, int* which, int* st);
+    bool handle_ilu_checked;     // seq_err_check() also when the handle's level 0 smooths with ILU (BSR handles only, as today)
+    bool mf_texts;               // the reference's older texts (pcg_mf_device, gmres_mf_device, minres_mf_device), as today
+    unsigned offered;            // methods of the family
+};
+
+// what a bound preconditioner keeps alive for the length of the solve
+struct PcState {
+    fasp_hip_amg*     h = nullptr;    // recognised device AMG handle, scalar ...
+    fasp_hip_amg_bsr* hb = nullptr;   // ... or block
+    IluDev*           ilu = nullptr;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp{nullptr, ilu_dev_destroy};
+    std::unique_ptr<TmpVec> ddiag, dz;   // device diagonal; output of the diagonal and of a foreign preconditioner
+    std::vector<double> hr, hz;          // host staging of a foreign preconditioner
+    double* out(int n) { if (!dz) dz.reset(new TmpVec(nullptr, (size_t)n)); return dz->d; }
+};
+
+int find_amg_csr(precond* pc, int n, PcState& S)   // fasp_hip_precond_fct or a reference-style fasp_precond_amg object
 {
-    if (ctx_init() < 0) die_no_device(fn);
-    if (!A || !b || !u || A->row != A->col || b->row != A->row || u->row != A->row) return ERROR_INPUT_PAR;
-    if (comm_size() > 1) return ERROR_INPUT_PAR;  // plug-in level: one GPU
-    const int n = b->row;
-    fasp_hip_amg* h = (pc && pc->fct == fasp_hip_precond_fct) ? static_cast<fasp_hip_amg*>(pc->data) : amg_handle_of_precond(pc);
-    if (h && (h->L.empty() || h->L[0].A.row != n)) return ERROR_INPUT_PAR;
-    std::unique_ptr<TmpCSR> own;
-    const DevCSR* dA = nullptr;
-    if (h && same_host_matrix(h->H.L[0].A, A)) dA = &h->L[0].A;  // the resident level-0 operator is A itself
-    else {
-        own.reset(new TmpCSR(A));
-        if (!own->ok) return ERROR_ALLOC_MEM;
-        dA = &own->D;
-    }
-    TmpVec db(b->val, n), du(u->val, n), dp(nullptr, n), dt(nullptr, n), dr(nullptr, n), dz(nullptr, n);
-    if (!db.d || !du.d || !dp.d || !dt.d || !dr.d || !dz.d) return ERROR_ALLOC_MEM;
-    std::vector<double> hr, hz;
-    std::vector<double*> ws;
-    size_t ws_len = 0;
-    double* hh = nullptr;
-    KOps K;
-    K.n = n; K.nvec = (size_t)n; K.fmt = "CSR"; K.dist = false;
-    K.halo = [](double*) { return 0; };
-    K.mxv = [dA](const double* x, double* y) { d_mxv(*dA, x, y); };
-    K.resid = [dA](const double* x, const double* bb, double* r) { d_resid(*dA, x, bb, r); };
-    K.mxv_dot = [dA](const double* x, double* y) {
-        CsrArgs a{}; a.x = x; a.y = y; a.dotv = x; a.partials = g_ctx.d_partials;
-        return launch_csr<OP_MXV_DOT>(*dA, a);
+    S.h = (pc && pc->fct == fasp_hip_precond_fct) ? static_cast<fasp_hip_amg*>(pc->data) : amg_handle_of_precond(pc);
+    return (S.h && (S.h->L.empty() || S.h->L[0].A.row != n)) ? ERROR_INPUT_PAR : FASP_SUCCESS;
+}
+int find_amg_matfree(precond* pc, int n, PcState& S)   // fasp_hip_precond_fct only
+{
+    S.h = (pc && pc->fct == fasp_hip_precond_fct) ? static_cast<fasp_hip_amg*>(pc->data) : nullptr;
+    return (S.h && (S.h->L.empty() || S.h->L[0].A.row != n)) ? ERROR_INPUT_PAR : FASP_SUCCESS;
+}
+int find_amg_bsr(precond* pc, int n, PcState& S)
+{
+    S.hb = (pc && pc->fct == fasp_hip_bsr_precond_fct) ? static_cast<fasp_hip_amg_bsr*>(pc->data) : nullptr;
+    return (S.hb && (S.hb->L.empty() || S.hb->L[0].n != n)) ? ERROR_INPUT_PAR : FASP_SUCCESS;
+}
+// the reference's diagonal preconditioner (PreCSR.c:172): recognised by its function pointer, applied on the device
+bool bind_diag_csr(precond* pc, int n, int, PcState& S, KOps& K, int* st)
+{
+    if (!(pc && pc->fct == fasp_precond_diag && pc->data && static_cast<dvector*>(pc->data)->row == n)) return false;
+    S.ddiag.reset(new TmpVec(static_cast<dvector*>(pc->data)->val, (size_t)n));
+    const double* dd = S.ddiag->d;
+    double* zz = S.out(n);
+    if (!dd || !zz) { *st = ERROR_ALLOC_MEM; return true; }
+    K.pc = [dd, zz, n](double* in, double** out) {
+        hipLaunchKernelGGL(k_diag_precond, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, dd, (const double*)in, zz);
+        *out = zz;
+        return 0;
     };
-    std::unique_ptr<TmpVec> ddiag;
-    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
-    int ilu_which_ = -1, ilu_st = FASP_SUCCESS;
-    IluDev* ilu = h ? nullptr : ilu_of_precond(pc, n, ilu_tmp, &ilu_which_, &ilu_st);
-    if (ilu_st < 0) return ilu_st;
-    if (h) {
-        K.pc = [h](double* in, double** out) { return precond_amg(h, in, out); };  // stays in HBM
-    } else if (ilu) {
-        // the reference's ILU preconditioner: recognised by its function pointer, both triangular solves on the device
+    return true;
+}
+// block-diagonal preconditioner of the reference (PreBSR.c:49): z_i = Dinv_i r_i on the device
+bool bind_diag_bsr(precond* pc, int n, int nb, PcState& S, KOps& K, int* st)
+{
+    if (!(pc && pc->fct == fasp_precond_dbsr_diag && pc->data && static_cast<precond_diag_bsr*>(pc->data)->diag.row == n * nb)) return false;
+    S.ddiag.reset(new TmpVec(static_cast<precond_diag_bsr*>(pc->data)->diag.val, (size_t)n * nb));
+    const double* dd = S.ddiag->d;
+    double* zz = S.out(n);
+    if (!dd || !zz) { *st = ERROR_ALLOC_MEM; return true; }
+    K.pc = [dd, zz, n, nb](double* in, double** out) {
+        hipLaunchKernelGGL(k_bsr_dinv_apply, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, nb, dd, (const double*)in, zz);
+        *out = zz;
+        return 0;
+    };
+    return true;
+}
+
+//                              fmt        ctx_first bad_bsr_dies refuse_multi_rank refuse_empty find_amg          borrow_resident fused_mxv_dot bind_diag      ilu_lookup          handle_ilu_checked mf_texts offered
+const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_diag_csr, ilu_of_precond,     false,             false,   K_OFFER_ALL};
+const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR};
+const KFamily FAMILY_MATFREE = {"MatFree", true,     false,       true,             true,        find_amg_matfree, false,          false,        nullptr,       ilu_of_precond,     false,             true,    K_OFFER_MATFREE};
+
+// K.pc for the caller's `precond`: a device AMG handle (S.h / S.hb, found by F.find_amg), a device ILU, a device (block-)
+// diagonal, else a foreign host function, staged through host memory.  pc == NULL: K.pc stays empty (identity).
+int bind_precond(const KFamily& F, precond* pc, int n, int nb, PcState& S, KOps& K)
+{
+    int ilu_which_ = -1, st = FASP_SUCCESS;
+    if (S.h) { fasp_hip_amg* h = S.h; K.pc = [h](double* in, double** out) { return precond_amg(h, in, out); }; return st; }  // stays in HBM
+    if (S.hb) { fasp_hip_amg_bsr* h = S.hb; K.pc = [h](double* in, double** out) { return precond_amg_bsr(h, in, out); }; return st; }
+    S.ilu = F.ilu_lookup(pc, n, S.ilu_tmp, &ilu_which_, &st);
+    if (st < 0) return st;
+    if (S.ilu) {
+        // the reference's (block) ILU preconditioner: recognised by its function pointer, both triangular solves on the device
+        IluDev* ilu = S.ilu;
         K.pc = [ilu, ilu_which_](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, ilu_which_, in, ilu->z); };
-    } else if (pc && pc->fct == fasp_precond_diag && pc->data && static_cast<dvector*>(pc->data)->row == n) {
-        // the reference's diagonal preconditioner: recognised by its function pointer, applied on the device
-        ddiag.reset(new TmpVec(static_cast<dvector*>(pc->data)->val, n));
-        if (!ddiag->d) return ERROR_ALLOC_MEM;
-        const double* dd = ddiag->d;
-        double* zz = dz.d;
-        K.pc = [dd, zz, n](double* in, double** out) {
-            hipLaunchKernelGGL(k_diag_precond, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, dd, (const double*)in, zz);
+        return st;
+    }
+    if (F.bind_diag && F.bind_diag(pc, n, nb, S, K, &st)) return st;
+    if (pc && pc->fct) {
+        // foreign preconditioner: a host function; the residual is staged through host memory
+        S.hr.resize((size_t)n); S.hz.resize((size_t)n);
+        double *hr = S.hr.data(), *hz = S.hz.data(), *zz = S.out(n);
+        if (!zz) return ERROR_ALLOC_MEM;
+        K.pc = [hr, hz, zz, n, pc](double* in, double** out) {
+            HIPCK(hipMemcpyAsync(hr, in, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
+            HIPCK(hipStreamSynchronize(g_ctx.stream));
+            pc->fct(hr, hz, pc->data);
+            HIPCK(hipMemcpyAsync(zz, hz, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
             *out = zz;
             return 0;
         };
-    } else if (pc && pc->fct) {
-        // foreign preconditioner: a host function; the residual is staged through host memory
-        hr.resize((size_t)n); hz.resize((size_t)n);
-        K.pc = [&, pc](double* in, double** out) {
-            HIPCK(hipMemcpyAsync(hr.data(), in, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
-            HIPCK(hipStreamSynchronize(g_ctx.stream));
-            pc->fct(hr.data(), hz.data(), pc->data);
-            HIPCK(hipMemcpyAsync(dz.d, hz.data(), sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
-            *out = dz.d;
-            return 0;
+    }
+    return st;
+}
+
+// where the operator comes from: a host dCSRmat, a host dBSRmat, or an mxv_matfree -- which is one of the two when
+// fasp_solver_matfree_init installed it (recognised by its function pointer), else a host callback
+struct KOperator {
+    enum Kind { CSR, BSR, HOST } kind;
+    const void* A;
+    const mxv_matfree* mf = nullptr;
+    bool valid = true;
+    KOperator(const dCSRmat* M) : kind(CSR), A(M) {}
+    KOperator(const dBSRmat* M) : kind(BSR), A(M) {}
+    KOperator(const mxv_matfree* m) : kind(HOST), A(nullptr), mf(m), valid(m && m->fct)
+    {
+        if (valid && m->fct == fasp_hip_mxv_csr) { kind = CSR; A = m->data; }
+        if (valid && m->fct == fasp_hip_mxv_bsr) { kind = BSR; A = m->data; }
+    }
+};
+
+int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op, dvector* b, dvector* u, precond* pc,
+                  const KParams& P)
+{
+    if (F.ctx_first && ctx_init() < 0) die_no_device(fn);
+    const dCSRmat* Ac = op.kind == KOperator::CSR ? static_cast<const dCSRmat*>(op.A) : nullptr;
+    const dBSRmat* Ab = op.kind == KOperator::BSR ? static_cast<const dBSRmat*>(op.A) : nullptr;
+    if (!op.valid || !b || !u || (op.kind != KOperator::HOST && !op.A)) return ERROR_INPUT_PAR;
+    const int n = b->row;
+    if (u->row != n || (F.refuse_empty && n <= 0)) return ERROR_INPUT_PAR;
+    if (Ac && (Ac->row != Ac->col || Ac->row != n)) return ERROR_INPUT_PAR;
+    if (Ab && (Ab->ROW != Ab->COL || Ab->ROW * Ab->nb != n)) return ERROR_INPUT_PAR;
+    if (F.refuse_multi_rank && comm_size() > 1) return ERROR_INPUT_PAR;  // plug-in level: one GPU
+    PcState S;
+    int st = F.find_amg(pc, n, S);
+    if (st < 0) return st;
+
+    // the operator: uploaded, or the handle's resident copy of it
+    KrylovWs ws;
+    KOps K;
+    K.n = n; K.nvec = (size_t)n; K.fmt = F.fmt; K.dist = false; K.ws = &ws;
+    K.halo = [](double*) { return 0; };
+    std::unique_ptr<TmpCSR> csr;
+    std::unique_ptr<TmpBSR> bsr;
+    std::unique_ptr<TmpVec> dy;
+    std::vector<double> hx, hy;
+    if (Ac) {
+        const DevCSR* dA = nullptr;
+        if (F.borrow_resident && S.h && same_host_matrix(S.h->H.L[0].A, Ac)) dA = &S.h->L[0].A;  // the resident level-0 operator is A itself
+        else {
+            csr.reset(new TmpCSR(Ac));
+            if (!csr->ok) return ERROR_ALLOC_MEM;
+            dA = &csr->D;
+        }
+        K.mxv = [dA](const double* x, double* y) { d_mxv(*dA, x, y); };
+        K.resid = [dA](const double* x, const double* bb, double* r) { d_resid(*dA, x, bb, r); };
+        if (F.fused_mxv_dot)
+            K.mxv_dot = [dA](const double* x, double* y) {
+                CsrArgs a{}; a.x = x; a.y = y; a.dotv = x; a.partials = g_ctx.d_partials;
+                return launch_csr<OP_MXV_DOT>(*dA, a);
+            };
+    } else if (Ab) {
+        bsr.reset(new TmpBSR(Ab));
+        if (!bsr->ok) { if (F.bad_bsr_dies) die_bsr(fn); return ERROR_ALLOC_MEM; }
+        const TmpBSR* Mp = bsr.get();
+        K.mxv = [Mp](const double* x, double* y) { bsr_mxv(*Mp, x, y); };
+        K.resid = [Mp](const double* x, const double* bb, double* r) { bsr_resid(*Mp, x, bb, r); };
+    } else {   // a host callback: its vectors are staged through host memory once per application
+        hx.resize((size_t)n); hy.resize((size_t)n);
+        dy.reset(new TmpVec(nullptr, (size_t)n));
+        if (!dy->d) return ERROR_ALLOC_MEM;
+        const mxv_matfree* mf = op.mf;
+        double *px = hx.data(), *py = hy.data(), *yy = dy->d;
+        auto host_mxv = [px, py, n, mf](const double* x, double* y) {
+            (void)hipMemcpyAsync(px, x, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream);
+            (void)hipStreamSynchronize(g_ctx.stream);
+            mf->fct(mf->data, px, py);
+            (void)hipMemcpyAsync(y, py, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream);
+            (void)hipStreamSynchronize(g_ctx.stream);  // hy is reused by the next application
+        };
+        K.mxv = host_mxv;
+        K.resid = [host_mxv, yy, n](const double* x, const double* bb, double* r) {  // r = 1.0 b + (-1.0) A x
+            host_mxv(x, yy);
+            (void)hipMemcpyAsync(r, yy, sizeof(double) * n, hipMemcpyDeviceToDevice, g_ctx.stream);
+            d_axpby(n, 1.0, bb, -1.0, r);
         };
     }
-    K.ws = &ws; K.ws_len = &ws_len; K.hh = &hh;
-    K.stats = nullptr;
+
+    TmpVec db(b->val, (size_t)n), du(u->val, (size_t)n);
+    if (!db.d || !du.d) return ERROR_ALLOC_MEM;
+    std::unique_ptr<TmpVec> cgv[3];   // p, t, r: only pcg_device takes scratch vectors from its caller
+    if (method == K_CG && !F.mf_texts)
+        for (auto& v : cgv) { v.reset(new TmpVec(nullptr, (size_t)n)); if (!v->d) return ERROR_ALLOC_MEM; }
+    double* const sp = cgv[0] ? cgv[0]->d : nullptr, *const stv = cgv[1] ? cgv[1]->d : nullptr, *const sr = cgv[2] ? cgv[2]->d : nullptr;
+    if ((st = bind_precond(F, pc, n, Ab ? Ab->nb : 1, S, K)) < 0) return st;
     Hist   H{nullptr, 0, 0};
     PcgOut po{BIGREAL, BIGREAL, BIGREAL};
-    int st;
-    if (which == 0) {
-        PcgVecs V{db.d, du.d, dp.d, dt.d, dr.d};
-        st = pcg_device(K, V, tol, abstol, MaxIt, StopType, PrtLvl, H, po);
-    } else if (which == 3) {
-        st = bicgstab_device(K, db.d, du.d, tol, MaxIt, PrtLvl, &H, &po);
-    } else if (which == 5) {
-        st = minres_device(K, db.d, du.d, tol, abstol, MaxIt, StopType, PrtLvl, &H, &po);
-    } else if (which == 6) {
-        st = gcg_device(K, db.d, du.d, tol, abstol, MaxIt, StopType, PrtLvl, &H, &po);
-    } else if (which == 7) {
-        st = gcr_device(K, db.d, du.d, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
-    } else {
-        st = gmres_device(K, db.d, du.d, which == 2 ? 1 : which == 4 ? 3 : 0, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
-    }
+    st = krylov_run(K, method, F.offered, F.mf_texts, P, db.d, du.d, sp, stv, sr, &H, &po);
     du.get(u->val);
-    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
-    for (double* q : ws) if (q) (void)hipFree(q);
-    if (hh) (void)hipFree(hh);
+    // a single-launch ILU solve (of the preconditioner, or of a block handle's cycle) that timed out
+    if ((S.ilu || (F.handle_ilu_checked && S.hb && S.hb->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
     return st;
 }
 }  // namespace
@@ -1387,56 +1444,56 @@ int fasp_solver_dcsr_pcg(dCSRmat* A, dvector* b, dvector* u, precond* pc, const 
                          const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 0, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_CG, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 // KryPgmres.c:66
 int fasp_solver_dcsr_pgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                             const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 4, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_GMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 // KryPvgmres.c:66
 int fasp_solver_dcsr_pvgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                              const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 1, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_VGMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 // KryPbcgs.c:62
 int fasp_solver_dcsr_pbcgs(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                            const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 3, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_BiCGstab, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 // KryPminres.c:61
 int fasp_solver_dcsr_pminres(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                              const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 5, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_MinRes, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 // KryPgcg.c:60
 int fasp_solver_dcsr_pgcg(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                           const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 6, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_GCG, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 // KryPgcr.c:55
 int fasp_solver_dcsr_pgcr(dCSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                           const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 7, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_GCR, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 // KryPvfgmres.c:67
 int fasp_solver_dcsr_pvfgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                               const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin(__func__, 2, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_CSR, K_VFGMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 
 // ---- the same plug-in level for block matrices ---------------------------------
@@ -1474,113 +1531,36 @@ void fasp_hip_bsr_precond_free(precond* pc)
     std::free(pc);
 }
 
-namespace {
-int krylov_plugin_bsr(const char* fn, int which, dBSRmat* A, dvector* b, dvector* u, precond* pc, double tol,
-                      double abstol, int MaxIt, short restart, short StopType, short PrtLvl)
-{
-    if (!A || !b || !u || A->ROW != A->COL || b->row != A->ROW * A->nb || u->row != b->row) return ERROR_INPUT_PAR;
-    TmpBSR M(A);
-    if (!M.ok) die_bsr(fn);
-    const int n = b->row;
-    fasp_hip_amg_bsr* h = (pc && pc->fct == fasp_hip_bsr_precond_fct) ? static_cast<fasp_hip_amg_bsr*>(pc->data) : nullptr;
-    if (h && (h->L.empty() || h->L[0].n != n)) return ERROR_INPUT_PAR;
-    TmpVec db(b->val, n), du(u->val, n), dp(nullptr, n), dt(nullptr, n), dr(nullptr, n), dz(nullptr, n);
-    if (!db.d || !du.d || !dp.d || !dt.d || !dr.d || !dz.d) return ERROR_ALLOC_MEM;
-    std::vector<double> hr, hz;
-    std::vector<double*> ws;
-    size_t ws_len = 0;
-    double* hh = nullptr;
-    KOps K;
-    K.n = n; K.nvec = (size_t)n; K.fmt = "BSR"; K.dist = false;
-    K.halo = [](double*) { return 0; };
-    const TmpBSR* Mp = &M;
-    K.mxv = [Mp](const double* x, double* y) { bsr_mxv(*Mp, x, y); };
-    K.resid = [Mp](const double* x, const double* bb, double* r) { bsr_resid(*Mp, x, bb, r); };
-    std::unique_ptr<TmpVec> ddiag;
-    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
-    int ilu_st = FASP_SUCCESS;
-    IluDev* ilu = h ? nullptr : ilu_of_precond_bsr(pc, n, ilu_tmp, &ilu_st);
-    if (ilu_st < 0) return ilu_st;
-    if (h) {
-        K.pc = [h](double* in, double** out) { return precond_amg_bsr(h, in, out); };
-    } else if (ilu) {
-        // the reference's block ILU preconditioner (PreBSR.c:347): recognised by its function pointer, both block
-        // triangular solves on the device
-        K.pc = [ilu](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, 0, in, ilu->z); };
-    } else if (pc && pc->fct == fasp_precond_dbsr_diag && pc->data &&
-               static_cast<precond_diag_bsr*>(pc->data)->diag.row == A->ROW * A->nb * A->nb) {
-        // block-diagonal preconditioner of the reference (PreBSR.c:49): z_i = Dinv_i r_i on the device
-        ddiag.reset(new TmpVec(static_cast<precond_diag_bsr*>(pc->data)->diag.val, (size_t)A->ROW * A->nb * A->nb));
-        if (!ddiag->d) return ERROR_ALLOC_MEM;
-        const double* dd = ddiag->d;
-        double* zz = dz.d;
-        const int nb = A->nb;
-        K.pc = [dd, zz, n, nb](double* in, double** out) {
-            hipLaunchKernelGGL(k_bsr_dinv_apply, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, nb, dd, (const double*)in, zz);
-            *out = zz;
-            return 0;
-        };
-    } else if (pc && pc->fct) {
-        hr.resize((size_t)n); hz.resize((size_t)n);
-        K.pc = [&, pc](double* in, double** out) {
-            HIPCK(hipMemcpyAsync(hr.data(), in, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
-            HIPCK(hipStreamSynchronize(g_ctx.stream));
-            pc->fct(hr.data(), hz.data(), pc->data);
-            HIPCK(hipMemcpyAsync(dz.d, hz.data(), sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
-            *out = dz.d;
-            return 0;
-        };
-    }
-    K.ws = &ws; K.ws_len = &ws_len; K.hh = &hh;
-    Hist   H{nullptr, 0, 0};
-    PcgOut po{BIGREAL, BIGREAL, BIGREAL};
-    int st;
-    if (which == 0) {
-        PcgVecs V{db.d, du.d, dp.d, dt.d, dr.d};
-        st = pcg_device(K, V, tol, abstol, MaxIt, StopType, PrtLvl, H, po);
-    } else if (which == 3) {
-        st = bicgstab_device(K, db.d, du.d, tol, MaxIt, PrtLvl, &H, &po);
-    } else {
-        st = gmres_device(K, db.d, du.d, which == 2 ? 1 : which == 4 ? 3 : 0, tol, abstol, MaxIt, restart, StopType, PrtLvl, &H, &po);
-    }
-    du.get(u->val);
-    if ((ilu || (h && h->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;   // a single-launch ILU solve that timed out
-    for (double* q : ws) if (q) (void)hipFree(q);
-    if (hh) (void)hipFree(hh);
-    return st;
-}
-}  // namespace
-
 // KryPcg.c:386, KryPbcgs.c:400, KryPgmres.c:357, KryPvgmres.c:416, KryPvfgmres.c:386
 int fasp_solver_dbsr_pcg(dBSRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                          const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin_bsr(__func__, 0, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_BSR, K_CG, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 int fasp_solver_dbsr_pbcgs(dBSRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                            const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin_bsr(__func__, 3, A, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_BSR, K_BiCGstab, A, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 int fasp_solver_dbsr_pgmres(dBSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                             const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin_bsr(__func__, 4, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_BSR, K_GMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 int fasp_solver_dbsr_pvgmres(dBSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                              const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin_bsr(__func__, 1, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_BSR, K_VGMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 int fasp_solver_dbsr_pvfgmres(dBSRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                               const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_plugin_bsr(__func__, 2, A, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_BSR, K_VFGMRES, A, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 
 // ---------------------------------------------------------------------------
@@ -1618,8 +1598,7 @@ int fasp_solver_dcsr_itsolver(dCSRmat* A, dvector* b, dvector* x, precond* pc, I
     const int MaxIt = itparam->maxit;
     const double tol = itparam->tol, abstol = itparam->abstol, t0 = wall_seconds();
     int iter;
-    if (tol < SMALLREAL) std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
-    if (MaxIt <= 0) std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+    its_check(tol, MaxIt);
     switch (itparam->itsolver_type) {
         case SOLVER_CG: iter = fasp_solver_dcsr_pcg(A, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
         case SOLVER_BiCGstab: iter = fasp_solver_dcsr_pbcgs(A, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
@@ -1633,7 +1612,7 @@ int fasp_solver_dcsr_itsolver(dCSRmat* A, dvector* b, dvector* x, precond* pc, I
             std::printf("### ERROR: Unknown iterative solver type %d! [%s]\n", itparam->itsolver_type, __func__);
             return ERROR_SOLVER_TYPE;
     }
-    if ((prtlvl >= PRINT_SOME) && (iter >= 0)) std::printf("Iterative method costs %.4f seconds.\n", wall_seconds() - t0);
+    print_itsolver_time(prtlvl, iter, wall_seconds() - t0);
     return iter;
 }
 // SolCSR.c:245
@@ -1672,8 +1651,7 @@ int fasp_solver_dbsr_itsolver(dBSRmat* A, dvector* b, dvector* x, precond* pc, I
     const int MaxIt = itparam->maxit;
     const double tol = itparam->tol, abstol = itparam->abstol, t0 = wall_seconds();
     int iter;
-    if (tol < SMALLREAL) std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
-    if (MaxIt <= 0) std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+    its_check(tol, MaxIt);
     switch (itparam->itsolver_type) {
         case SOLVER_CG: iter = fasp_solver_dbsr_pcg(A, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
         case SOLVER_BiCGstab: iter = fasp_solver_dbsr_pbcgs(A, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
@@ -1684,7 +1662,7 @@ int fasp_solver_dbsr_itsolver(dBSRmat* A, dvector* b, dvector* x, precond* pc, I
             std::printf("### ERROR: Unknown iterative solver type %d! [%s]\n", itparam->itsolver_type, __func__);
             return ERROR_SOLVER_TYPE;
     }
-    if ((prtlvl >= PRINT_SOME) && (iter >= 0)) std::printf("Iterative method costs %.4f seconds.\n", wall_seconds() - t0);
+    print_itsolver_time(prtlvl, iter, wall_seconds() - t0);
     return iter;
 }
 // SolBSR.c:145
@@ -1751,145 +1729,49 @@ void fasp_solver_matfree_init(int matrix_format, mxv_matfree* mf, void* A)
     mf->data = A;
 }
 
-namespace {
-// which: 0 CG, 1 VGMRES, 2 VFGMRES, 3 BiCGstab, 4 GMRES, 5 MinRes, 6 GCG
-int krylov_matfree(const char* fn, int which, mxv_matfree* mf, dvector* b, dvector* u, precond* pc, double tol,
-                   double abstol, int MaxIt, short restart, short StopType, short PrtLvl)
-{
-    if (ctx_init() < 0) die_no_device(fn);
-    if (!mf || !mf->fct || !b || !u || b->row != u->row || b->row <= 0) return ERROR_INPUT_PAR;
-    if (comm_size() > 1) return ERROR_INPUT_PAR;
-    const int n = b->row;
-    std::unique_ptr<TmpCSR> csr;
-    std::unique_ptr<fasp_bsr::TmpBSR> bsr;
-    KOps K;
-    K.n = n; K.nvec = (size_t)n; K.fmt = "MatFree"; K.dist = false;
-    K.halo = [](double*) { return 0; };
-    TmpVec db(b->val, n), du(u->val, n), dz(nullptr, n), dy(nullptr, n);
-    if (!db.d || !du.d || !dz.d || !dy.d) return ERROR_ALLOC_MEM;
-    std::vector<double> hx, hy, hr, hz;
-    if (mf->fct == fasp_hip_mxv_csr) {
-        const dCSRmat* A = static_cast<const dCSRmat*>(mf->data);
-        if (!A || A->row != n || A->col != n) return ERROR_INPUT_PAR;
-        csr.reset(new TmpCSR(A));
-        if (!csr->ok) return ERROR_ALLOC_MEM;
-        const DevCSR* dA = &csr->D;
-        K.mxv = [dA](const double* x, double* y) { d_mxv(*dA, x, y); };
-        K.resid = [dA](const double* x, const double* bb, double* r) { d_resid(*dA, x, bb, r); };
-    } else if (mf->fct == fasp_hip_mxv_bsr) {
-        const dBSRmat* A = static_cast<const dBSRmat*>(mf->data);
-        if (!A || A->ROW * A->nb != n || A->ROW != A->COL) return ERROR_INPUT_PAR;
-        bsr.reset(new fasp_bsr::TmpBSR(A));
-        if (!bsr->ok) return ERROR_ALLOC_MEM;
-        const fasp_bsr::TmpBSR* Mp = bsr.get();
-        K.mxv = [Mp](const double* x, double* y) { fasp_bsr::bsr_mxv(*Mp, x, y); };
-        K.resid = [Mp](const double* x, const double* bb, double* r) { fasp_bsr::bsr_resid(*Mp, x, bb, r); };
-    } else {
-        hx.resize((size_t)n); hy.resize((size_t)n);
-        auto host_mxv = [&, mf](const double* x, double* y) {
-            (void)hipMemcpyAsync(hx.data(), x, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream);
-            (void)hipStreamSynchronize(g_ctx.stream);
-            mf->fct(mf->data, hx.data(), hy.data());
-            (void)hipMemcpyAsync(y, hy.data(), sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream);
-            (void)hipStreamSynchronize(g_ctx.stream);  // hy is reused by the next application
-        };
-        K.mxv = host_mxv;
-        K.resid = [&, host_mxv](const double* x, const double* bb, double* r) {  // r = 1.0 b + (-1.0) A x
-            host_mxv(x, dy.d);
-            (void)hipMemcpyAsync(r, dy.d, sizeof(double) * n, hipMemcpyDeviceToDevice, g_ctx.stream);
-            d_axpby(n, 1.0, bb, -1.0, r);
-        };
-    }
-    fasp_hip_amg* h = (pc && pc->fct == fasp_hip_precond_fct) ? static_cast<fasp_hip_amg*>(pc->data) : nullptr;
-    if (h && (h->L.empty() || h->L[0].A.row != n)) return ERROR_INPUT_PAR;
-    std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp(nullptr, ilu_dev_destroy);
-    int ilu_which_ = -1, ilu_st = FASP_SUCCESS;
-    IluDev* ilu = h ? nullptr : ilu_of_precond(pc, n, ilu_tmp, &ilu_which_, &ilu_st);
-    if (ilu_st < 0) return ilu_st;
-    if (h) {
-        K.pc = [h](double* in, double** out) { return precond_amg(h, in, out); };
-    } else if (ilu) {
-        K.pc = [ilu, ilu_which_](double* in, double** out) { *out = ilu->z; return ilu_apply(ilu, ilu_which_, in, ilu->z); };
-    } else if (pc && pc->fct) {
-        hr.resize((size_t)n); hz.resize((size_t)n);
-        K.pc = [&, pc](double* in, double** out) {
-            HIPCK(hipMemcpyAsync(hr.data(), in, sizeof(double) * n, hipMemcpyDeviceToHost, g_ctx.stream));
-            HIPCK(hipStreamSynchronize(g_ctx.stream));
-            pc->fct(hr.data(), hz.data(), pc->data);
-            HIPCK(hipMemcpyAsync(dz.d, hz.data(), sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
-            *out = dz.d;
-            return 0;
-        };
-    }
-    std::vector<double*> ws;
-    size_t ws_len = 0;
-    double* hh = nullptr;
-    K.ws = &ws; K.ws_len = &ws_len; K.hh = &hh;
-    K.stats = nullptr;
-    Hist   H{nullptr, 0, 0};
-    PcgOut po{BIGREAL, BIGREAL, BIGREAL};
-    int st;
-    switch (which) {
-        case 0: st = pcg_mf_device(K, db.d, du.d, tol, abstol, MaxIt, StopType, PrtLvl, &po); break;
-        case 1: st = gmres_mf_device(K, true, false, db.d, du.d, tol, MaxIt, restart, StopType, PrtLvl, &po); break;
-        case 2: st = gmres_mf_device(K, true, true, db.d, du.d, tol, MaxIt, restart, StopType, PrtLvl, &po); break;
-        case 3: st = bicgstab_device(K, db.d, du.d, tol, MaxIt, PrtLvl, &H, &po); break;
-        case 4: st = gmres_mf_device(K, false, false, db.d, du.d, tol, MaxIt, restart, StopType, PrtLvl, &po); break;
-        case 5: st = minres_mf_device(K, db.d, du.d, tol, abstol, MaxIt, StopType, PrtLvl, &po); break;
-        case 6: st = gcg_device(K, db.d, du.d, tol, abstol, MaxIt, StopType, PrtLvl, &H, &po); break;
-        default: st = ERROR_SOLVER_TYPE;
-    }
-    du.get(u->val);
-    if (ilu && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
-    for (double* q : ws) if (q) (void)hipFree(q);
-    if (hh) (void)hipFree(hh);
-    return st;
-}
-}  // namespace
-
 // KryPcg.c:1260, KryPbcgs.c:1349, KryPgcg.c:213, KryPgmres.c:1309, KryPvgmres.c:1468, KryPvfgmres.c:1026
 int fasp_solver_pcg(mxv_matfree* mf, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                     const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 0, mf, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_CG, mf, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 int fasp_solver_pbcgs(mxv_matfree* mf, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                       const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 3, mf, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_BiCGstab, mf, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 int fasp_solver_pgcg(mxv_matfree* mf, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                      const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 6, mf, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_GCG, mf, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 int fasp_solver_pgmres(mxv_matfree* mf, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                        const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 4, mf, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_GMRES, mf, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 int fasp_solver_pvgmres(mxv_matfree* mf, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                         const int MaxIt, short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 1, mf, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_VGMRES, mf, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 int fasp_solver_pvfgmres(mxv_matfree* mf, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
                          const int MaxIt, const short restart, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 2, mf, b, x, pc, tol, abstol, MaxIt, restart, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_VFGMRES, mf, b, x, pc, {tol, abstol, MaxIt, restart, StopType, PrtLvl});
 }
 // KryPminres.c:1283: the reference's older MinRes text for mxv_matfree (minres_mf_device, krylov.hip.h)
 int fasp_solver_pminres(mxv_matfree* mf, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                         const int MaxIt, const short StopType, const short PrtLvl)
 {
     FASP_ENTRY();
-    return krylov_matfree(__func__, 5, mf, b, u, pc, tol, abstol, MaxIt, 0, StopType, PrtLvl);
+    return krylov_plugin(__func__, FAMILY_MATFREE, K_MinRes, mf, b, u, pc, {tol, abstol, MaxIt, 0, StopType, PrtLvl});
 }
 
 // SolMatFree.c:58: dispatch on itsolver_type
@@ -1902,8 +1784,7 @@ int fasp_solver_itsolver(mxv_matfree* mf, dvector* b, dvector* x, precond* pc, I
     const double tol = itparam->tol, abstol = itparam->abstol;
     const double t0 = wall_seconds();
     int iter = ERROR_SOLVER_TYPE;
-    if (tol < SMALLREAL) std::printf("### WARNING: Convergence tolerance is too small! [%s:%d]\n", "ITS_CHECK", 74);
-    if (MaxIt <= 0) std::printf("### WARNING: Max number of iterations must be POSITIVE! [%s:%d]\n", "ITS_CHECK", 78);
+    its_check(tol, MaxIt);
     switch (itparam->itsolver_type) {
         case SOLVER_CG: iter = fasp_solver_pcg(mf, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
         case SOLVER_BiCGstab: iter = fasp_solver_pbcgs(mf, b, x, pc, tol, abstol, MaxIt, stop_type, prtlvl); break;
@@ -1916,7 +1797,7 @@ int fasp_solver_itsolver(mxv_matfree* mf, dvector* b, dvector* x, precond* pc, I
             std::printf("### ERROR: Unknown iterative solver type %d! [%s]\n", itparam->itsolver_type, __func__);
             return ERROR_SOLVER_TYPE;
     }
-    if ((prtlvl >= PRINT_SOME) && (iter >= 0)) std::printf("Iterative method costs %.4f seconds.\n", wall_seconds() - t0);
+    print_itsolver_time(prtlvl, iter, wall_seconds() - t0);
     return iter;
 }
 

@@ -152,3 +152,74 @@ def test_gpu_matfree_pcg_with_device_amg():
     L.fasp_hip_precond_free(pc)
     assert s1 == s0
     assert np.abs(x1 - x0).max() <= 1e-10 * np.abs(x0).max()
+
+
+REFUSALS = [("csr", "length"), ("csr", "nonsquare"), ("csr", "amg_size"), ("bsr", "length"), ("bsr", "nonsquare"),
+            ("mf", "length"), ("mf", "amg_size"), ("mf", "null_fct")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family,case", REFUSALS)
+def test_gpu_plugin_pcg_refuses_bad_arguments(family, case):
+    """What fasp_solver_dcsr_pcg / fasp_solver_dbsr_pcg / fasp_solver_pcg refuse with ERROR_INPUT_PAR: vectors of different
+    lengths, a non-square matrix, a device AMG built for another size, an operator without a function."""
+    L = fa.lib()
+    ia, ja, a, f, ue = poisson7pt(8)
+    if family == "bsr":
+        ia, ja, val, nb = poisson7pt_bsr(4)
+        f = np.ones((len(ia) - 1) * nb)
+    n = len(f)
+    x = np.zeros(n + 1)
+    bv, fk = T.as_vec(f); xv = T.dvector(n + 1 if case == "length" else n, T.dp(x))
+    ncol = len(ia) if case == "nonsquare" else None
+    pc = None
+    if case == "amg_size":
+        ia6, ja6, a6, f6, ue6 = poisson7pt(6)
+        itp, amgp = default_params(); amgp.smoother = T.SMOOTHER_JACOBI; amgp.relaxation = 0.6667
+        A6, keep6 = T.as_csr(ia6, ja6, a6)
+        pc = L.fasp_hip_precond_setup(C.byref(A6), C.byref(amgp))
+        assert pc
+    tail = (pc, 1e-8, 1e-18, 100, 1, 0)
+    if family == "csr":
+        A, keep = T.as_csr(ia, ja, a, ncol)
+        st = L.fasp_solver_dcsr_pcg(C.byref(A), C.byref(bv), C.byref(xv), *tail)
+    elif family == "bsr":
+        A, keep = T.as_bsr(ia, ja, val, nb, ncol)
+        st = L.fasp_solver_dbsr_pcg(C.byref(A), C.byref(bv), C.byref(xv), *tail)
+    else:
+        A, keep = T.as_csr(ia, ja, a)
+        mf = MF(); L.fasp_solver_matfree_init(1, C.byref(mf), C.byref(A))
+        if case == "null_fct":
+            mf.fct = None
+        fn = L.fasp_solver_pcg
+        fn.argtypes = [C.c_void_p, C.POINTER(T.dvector), C.POINTER(T.dvector), C.c_void_p, C.c_double, C.c_double, C.c_int,
+                       C.c_short, C.c_short]
+        fn.restype = C.c_int
+        st = fn(C.addressof(mf), C.byref(bv), C.byref(xv), *tail)
+    if pc:
+        L.fasp_hip_precond_free(pc)
+    assert st == T.ERROR_INPUT_PAR
+    assert not x.any()
+
+
+@pytest.mark.gpu
+@needs_ref
+@pytest.mark.parametrize("which", [0, 1])
+def test_gpu_matfree_reference_diag_precond(which):
+    """fasp_solver_pcg / fasp_solver_pvgmres with the reference's own diagonal preconditioner, pc = {dvector, fasp_precond_diag}:
+    the matrix-free family applies it as a host function, as the reference does."""
+    ia, ja, a, f, ue = poisson7pt(10)
+    f = rhs(len(f))
+    n = len(f)
+    d = np.array([a[ia[i]:ia[i + 1]][ja[ia[i]:ia[i + 1]] == i][0] for i in range(n)])
+
+    def run(lib_):
+        A, keep = T.as_csr(ia, ja, a)
+        mf = MF(); lib_.fasp_solver_matfree_init(1, C.byref(mf), C.byref(A))
+        dv, dk = T.as_vec(d)
+        pc = T.precond(C.cast(C.pointer(dv), C.c_void_p), C.cast(lib_.fasp_precond_diag, T.PRECOND_FCT))
+        return call_mf(lib_, which, mf, f, C.cast(C.pointer(pc), C.c_void_p))
+    s1, x1 = run(ref())
+    s2, x2 = run(fa.lib())
+    assert s1 == s2 and s1 > 5
+    assert np.abs(x1 - x2).max() <= 1e-9 * np.abs(x1).max()

@@ -75,3 +75,60 @@ def test_unknown_solver_type_is_refused():
     itp, _ = default_params(); itp.itsolver_type = 13   # SOLVER_SMinRes belongs to fasp_solver_dcsr_itsolver_s
     st, x = _call(fa.lib(), "fasp_solver_dcsr_krylov", A, f, itp)
     assert st == T.ERROR_SOLVER_TYPE and not x.any()
+
+
+# ---- resident handles: the Krylov workspace a handle owns ------------------------------------------------
+def _jacobi_params(solver, restart):
+    itp, amgp = default_params()
+    itp.tol = 1e-8; itp.itsolver_type = solver; itp.restart = restart
+    amgp.smoother = T.SMOOTHER_JACOBI; amgp.relaxation = 0.6667
+    return itp, amgp
+
+
+def _same(r1, r2):
+    """status, solution and residual history of two solves, bit for bit"""
+    return r1[0] == r2[0] and np.array_equal(r1[1], r2[1]) and np.array_equal(r1[2], r2[2])
+
+
+def test_gpu_workspace_reuse_across_methods():
+    """One handle, methods whose workspaces differ in the number of vectors, one after the other: every driver writes a
+    workspace vector before it reads it, so a solve does not see what the solve before it left behind."""
+    ia, ja, a, f, ue = poisson7pt(8)
+    f = _rhs(len(f))
+    order = [(T.SOLVER_VGMRES, 5), (T.SOLVER_BiCGstab, 5), (T.SOLVER_VFGMRES, 30), (T.SOLVER_MinRes, 30), (T.SOLVER_VGMRES, 5)]
+    H = fa.AMG(ia, ja, a, _jacobi_params(1, 30)[1])
+    got = [H.solve(f, _jacobi_params(solver, restart)[0])[:3] for solver, restart in order]
+    H.close()
+    assert all(g[0] > 0 for g in got)
+    assert _same(got[0], got[4])
+    for (solver, restart), g in zip(order, got):
+        F = fa.AMG(ia, ja, a, _jacobi_params(1, 30)[1])
+        fresh = F.solve(f, _jacobi_params(solver, restart)[0])[:3]
+        F.close()
+        assert _same(g, fresh), (solver, restart)
+
+
+def test_gpu_two_handles_interleaved():
+    """A CSR and a BSR handle alive together, solved in turn and destroyed in the opposite order of creation: each handle
+    owns its Krylov workspace, the results are those of the handles alone."""
+    from _libs import bsr_params
+    ia, ja, a, f, ue = poisson7pt(8)
+    f = _rhs(len(f))
+    bia, bja, bval, nb = poisson7pt_bsr(6)
+    bf = _rhs((len(bia) - 1) * nb)
+    H = fa.AMG(ia, ja, a, _jacobi_params(1, 30)[1])
+    G = fa.BSRAMG(bia, bja, bval, nb, bsr_params()[1])
+    c1 = H.solve(f, _jacobi_params(T.SOLVER_VGMRES, 30)[0])[:3]
+    b1 = G.solve(bf, bsr_params(T.SOLVER_VGMRES)[0])[:3]
+    c2 = H.solve(f, _jacobi_params(T.SOLVER_VGMRES, 30)[0])[:3]
+    G.free()
+    H.close()
+    assert c1[0] > 0 and b1[0] > 0
+    assert _same(c1, c2)
+    H = fa.AMG(ia, ja, a, _jacobi_params(1, 30)[1])
+    c0 = H.solve(f, _jacobi_params(T.SOLVER_VGMRES, 30)[0])[:3]
+    H.close()
+    G = fa.BSRAMG(bia, bja, bval, nb, bsr_params()[1])
+    b0 = G.solve(bf, bsr_params(T.SOLVER_VGMRES)[0])[:3]
+    G.free()
+    assert _same(c1, c0) and _same(b1, b0)
