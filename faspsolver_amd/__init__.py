@@ -57,6 +57,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_ilu_dbsr_setup", "fasp_precond_dbsr_ilu", "fasp_solver_dbsr_krylov_ilu", "fasp_smoother_dbsr_ilu",
     "fasp_fwrapper_dbsr_krylov_ilu_",
     "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
+    "fasp_hip_bsr_sweep",
 ]
 
 
@@ -112,6 +113,8 @@ def lib():
     L.fasp_dbsr_getdiaginv.argtypes = [P(T.dBSRmat)]
     L.fasp_dbsr_getdiaginv.restype = T.dvector
     L.fasp_smoother_dbsr_jacobi1.argtypes = [P(T.dBSRmat), P(T.dvector), P(T.dvector), T.c_double_p]
+    L.fasp_hip_bsr_sweep.argtypes = [P(T.dBSRmat), T.c_double_p, T.c_double_p, T.c_double_p, C.c_int, C.c_int, C.c_double,
+                                     P(C.c_int)]
     L.fasp_hip_time_bsr_mxv.argtypes = [P(T.dBSRmat), C.c_int]
     L.fasp_hip_time_bsr_mxv.restype = C.c_double
     L.fasp_solver_dcsr_pcg.argtypes = [P(T.dCSRmat), P(T.dvector), P(T.dvector), P(T.precond), C.c_double,

@@ -127,33 +127,30 @@ static void bsr_jacobi(BsrLevel& Lv)
     std::swap(Lv.x, Lv.x2);
 }
 
-// One sequential block sweep (Gauss-Seidel or SOR, ascending or descending) as level-scheduled launches:
-// the rows of a dependency level are mutually uncoupled, so the result is the sequential sweep.
-static int bsr_seq_sweep(fasp_hip_amg_bsr* h, int level, bool descend, bool sor, double w)
+// Level schedule of one sequential block sweep over all block rows, ascending or descending, from the block pattern
+// alone (build_schedule does not read values)
+static int bsr_seq_schedule(int ROW, int COL, int NNZ, const int* ia, const int* ja, bool descend, DevLevel::Sched& S)
 {
-    BsrLevel& Lv = h->L[level];
-    DevLevel::Sched& S = Lv.sched[descend ? 1 : 0];
-    const TmpBSR& M = *Lv.A;
-    if (!S.built) {
-        const HostBSR& A = h->H.L[level].A;
-        HostCSR pat;  // block pattern only (build_schedule does not read values)
-        pat.row = A.ROW; pat.col = A.COL; pat.nnz = A.NNZ;
-        pat.ia.alloc((size_t)A.ROW + 1); pat.ja.alloc((size_t)std::max(A.NNZ, 1));
-        std::memcpy(pat.ia.data(), A.ia.data(), sizeof(int) * ((size_t)A.ROW + 1));
-        std::memcpy(pat.ja.data(), A.ja.data(), sizeof(int) * (size_t)A.NNZ);
-        std::vector<int> seq((size_t)A.ROW);
-        for (int i = 0; i < A.ROW; ++i) seq[(size_t)i] = descend ? A.ROW - 1 - i : i;
-        const int st = build_schedule(pat, seq, S);
-        if (st < 0) return st;
-    }
-    if (Lv.x_zero) { HIPCK(hipMemsetAsync(Lv.x, 0, sizeof(double) * Lv.n, g_ctx.stream)); Lv.x_zero = false; }
+    HostCSR pat;
+    pat.row = ROW; pat.col = COL; pat.nnz = NNZ;
+    pat.ia.alloc((size_t)ROW + 1); pat.ja.alloc((size_t)std::max(NNZ, 1));
+    std::memcpy(pat.ia.data(), ia, sizeof(int) * ((size_t)ROW + 1));
+    std::memcpy(pat.ja.data(), ja, sizeof(int) * (size_t)NNZ);
+    std::vector<int> seq((size_t)ROW);
+    for (int i = 0; i < ROW; ++i) seq[(size_t)i] = descend ? ROW - 1 - i : i;
+    return build_schedule(pat, seq, S);
+}
+
+// The launches of one scheduled block sweep of x in place, one per dependency level
+static int bsr_seq_launch(const TmpBSR& M, const DevLevel::Sched& S, const double* b, const double* dinv, double* x,
+                          bool sor, double w)
+{
     const int nlev = (int)S.ptr.size() - 1;
     for (int l = 0; l < nlev; ++l) {
         const int lo = S.ptr[l], hi = S.ptr[l + 1];
         const int grid = std::max(1, std::min(MAXGRID, (hi - lo + BLOCK - 1) / BLOCK));
 #define BSEQ_LAUNCH(NBV) hipLaunchKernelGGL((k_bsr_seq_level<NBV>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, \
-        (const int*)S.d_order, lo, hi, (const int*)M.ia, (const int*)M.ja, (const double*)M.val, (const double*)Lv.b, \
-        (const double*)Lv.dinv, Lv.x, sor ? 1 : 0, w)
+        (const int*)S.d_order, lo, hi, (const int*)M.ia, (const int*)M.ja, (const double*)M.val, b, dinv, x, sor ? 1 : 0, w)
         switch (M.nb) {
             case 1: BSEQ_LAUNCH(1); break;
             case 2: BSEQ_LAUNCH(2); break;
@@ -167,6 +164,21 @@ static int bsr_seq_sweep(fasp_hip_amg_bsr* h, int level, bool descend, bool sor,
 #undef BSEQ_LAUNCH
     }
     return FASP_SUCCESS;
+}
+
+// One sequential block sweep (Gauss-Seidel or SOR, ascending or descending) as level-scheduled launches:
+// the rows of a dependency level are mutually uncoupled, so the result is the sequential sweep.
+static int bsr_seq_sweep(fasp_hip_amg_bsr* h, int level, bool descend, bool sor, double w)
+{
+    BsrLevel& Lv = h->L[level];
+    DevLevel::Sched& S = Lv.sched[descend ? 1 : 0];
+    if (!S.built) {
+        const HostBSR& A = h->H.L[level].A;
+        const int st = bsr_seq_schedule(A.ROW, A.COL, A.NNZ, A.ia.data(), A.ja.data(), descend, S);
+        if (st < 0) return st;
+    }
+    if (Lv.x_zero) { HIPCK(hipMemsetAsync(Lv.x, 0, sizeof(double) * Lv.n, g_ctx.stream)); Lv.x_zero = false; }
+    return bsr_seq_launch(*Lv.A, S, Lv.b, Lv.dinv, Lv.x, sor, w);
 }
 
 // smoother dispatch of fasp_solver_mgcycle_bsr, PreMGCycle.c:327-365 (pre) and :513-549 (post)

@@ -2026,6 +2026,27 @@ void fasp_smoother_dbsr_jacobi1(dBSRmat* A, dvector* b, dvector* u, double* diag
     dun.get(u->val);
 }
 
+// test entry: one block Gauss-Seidel / SOR sweep of a host matrix through the schedule and the launches of the cycle's sweeps
+int fasp_hip_bsr_sweep(const dBSRmat* A, const double* b, double* u, const double* diaginv, int descend, int sor, double w,
+                       int* nlevels)
+{
+    FASP_ENTRY();
+    if (!A || !b || !u || !diaginv || !nlevels || !A->IA || (A->NNZ > 0 && (!A->JA || !A->val))) return ERROR_INPUT_PAR;
+    if (A->nb < 1 || A->nb > 7 || A->storage_manner != 0 || A->ROW != A->COL || A->ROW < 0 || A->NNZ < 0) return ERROR_INPUT_PAR;
+    TmpBSR M(A);
+    if (!M.ok) return ERROR_MISC;   // no device (or no memory on it)
+    const size_t n = (size_t)A->ROW * A->nb;
+    TmpVec du(u, n), db(b, n), dd(diaginv, n * A->nb);
+    if (!du.d || !db.d || !dd.d) return ERROR_MISC;
+    DevLevel::Sched S;
+    int st = bsr_seq_schedule(A->ROW, A->COL, A->NNZ, A->IA, A->JA, descend != 0, S);
+    if (st >= 0) st = bsr_seq_launch(M, S, db.d, dd.d, du.d, sor != 0, w);
+    if (st >= 0) { *nlevels = (int)S.ptr.size() - 1; du.get(u); }
+    else (void)hipStreamSynchronize(g_ctx.stream);
+    S.release();
+    return st;
+}
+
 double fasp_hip_time_bsr_mxv(const dBSRmat* A, int reps)
 {
     FASP_ENTRY();

@@ -151,6 +151,12 @@ int  fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double
 int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red);
 /* ... and of a matrix given on the host, uploaded the way a level's A is; *kind_out (may be NULL) = 11 when its sliced-ELL form is in use */
 int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out);
+/* test entry: ONE sequential block sweep of the host matrix A (square, storage_manner 0, 1 <= nb <= 7, a diagonal block in every row) on the
+ * device, through the level schedule and the per-level launches the block AMG cycle smooths with: block Gauss-Seidel (sor = 0; w unused) or
+ * block SOR with weight w, rows ascending (descend = 0) or descending, u updated in place.  diaginv: the ROW inverse diagonal blocks
+ * (fasp_dbsr_getdiaginv).  *nlevels = dependency levels of the schedule (launches of the sweep).  Bad arguments (a NULL pointer, nb outside
+ * 1..7, storage_manner != 0, ROW != COL) return ERROR_INPUT_PAR and touch nothing; no usable device: ERROR_MISC. */
+int  fasp_hip_bsr_sweep(const dBSRmat* A, const double* b, double* u, const double* diaginv, int descend, int sor, double w, int* nlevels);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 

@@ -1,5 +1,6 @@
 """Loaders for the checker libraries used by the tests (oracle, reference build)."""
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -318,3 +319,166 @@ class OrcBSR:
                 R=None if last else (L.R.ROW, L.R.COL, L.R.NNZ) + bsr_arrays(L.R),
                 diaginv=d))
         self._buf = buf  # hierarchy memory is leaked with the buffer (test process only)
+
+
+def orc_bsr_ops():
+    """The oracle with the prototypes of its block operators set."""
+    o = oracle()
+    o.orc_bsr_mxv.argtypes = [C.POINTER(T.dBSRmat), T.c_double_p, T.c_double_p]
+    o.orc_bsr_aAxpy.argtypes = [C.c_double, C.POINTER(T.dBSRmat), T.c_double_p, T.c_double_p]
+    o.orc_bsr_getdiaginv.argtypes = [C.POINTER(T.dBSRmat)]
+    o.orc_bsr_getdiaginv.restype = T.c_double_p
+    o.orc_bsr_jacobi1.argtypes = [C.POINTER(T.dBSRmat), T.c_double_p, T.c_double_p, T.c_double_p]
+    o.orc_bsr_gs_sor.argtypes = [C.POINTER(T.dBSRmat), T.c_double_p, T.c_double_p, T.c_double_p, C.c_int, C.c_int, C.c_double]
+    o.orc_free.argtypes = [C.c_void_p]
+    return o
+
+
+def orc_diaginv(o, A):
+    """orc_bsr_getdiaginv as a numpy array."""
+    dp_ = o.orc_bsr_getdiaginv(C.byref(A))
+    d = np.ctypeslib.as_array(dp_, (A.ROW * A.nb * A.nb,)).copy()
+    o.orc_free(dp_)
+    return d
+
+
+SOR_WEIGHTS = (1.1, 1.0, 0.5)   # the block SOR weights the sweeps are compared at
+
+
+# --- irregular BSR matrices for the block row kernel (k_bsr_wstream) and the block sweeps ---------
+def bsr_tile(nb):
+    """(RW, CAPB, U) of k_bsr_wstream<nb, .>: block rows per wave tile, blocks per LDS chunk, blocks per round trip."""
+    return 64 // nb, 1536 // (nb * nb), 8 if nb <= 3 else 4
+
+
+def ragged_bsr(nb, seed, square=True, extra_cols=0):
+    """An irregular BSR matrix that reaches the edges of k_bsr_wstream<nb, .> a stencil never touches
+    -> (ROW, COL, ia, ja, val, lens); deterministic in (nb, seed, square, extra_cols).
+
+    ROW = max(13 RW + 1, 2 CAPB + 67), COL = ROW + extra_cols (extra_cols >= -50).  Values are standard normal.  Rows hold
+    1 .. 2U + 2 blocks (capped at COL) in distinct, unsorted columns, except row 0 (2 CAPB + 3 blocks: three LDS chunks),
+    rows RW - 1 and RW (empty: end of one wave tile, start of the next), rows 2 RW .. 3 RW - 1 (empty: a tile without
+    blocks), row 3 RW + 1 (one block) and the last row (CAPB + 1 blocks).  square: every row holds its diagonal block at a
+    random position, the empty rows become diagonal-only (the sweeps need a diagonal) and the diagonal block gets
+    I * 3 sqrt(4 nb len) added, which keeps one Gauss-Seidel / SOR sweep bounded.  Otherwise the empty rows stay empty and
+    the diagonal is nothing special."""
+    RW, CAPB, U = bsr_tile(nb)
+    nb2 = nb * nb
+    rng = np.random.default_rng(seed)
+    ROW = max(13 * RW + 1, 2 * CAPB + 67)
+    COL = ROW + extra_cols
+    assert not (square and extra_cols), "the square form has COL == ROW"
+    lens = np.minimum(rng.integers(1, 2 * U + 3, size=ROW), COL)
+    lens[0] = 2 * CAPB + 3
+    empty = np.r_[RW - 1, RW, 2 * RW:3 * RW]
+    lens[empty] = 1 if square else 0
+    lens[3 * RW + 1] = 1
+    lens[ROW - 1] = CAPB + 1
+    assert lens.max() <= COL
+    ia = np.zeros(ROW + 1, dtype=np.int32)
+    ia[1:] = np.cumsum(lens)
+    ja = np.empty(int(ia[-1]), dtype=np.int32)
+    for i in range(ROW):   # (the one per-row loop: a draw without replacement per row)
+        k = int(lens[i])
+        if square:
+            c = rng.choice(COL - 1, size=k - 1, replace=False)
+            c = np.append(c + (c >= i), i)
+        else:
+            c = rng.choice(COL, size=k, replace=False)
+        rng.shuffle(c)
+        ja[ia[i]:ia[i + 1]] = c
+    val = rng.standard_normal(int(ia[-1]) * nb2)
+    if square:
+        rows = np.repeat(np.arange(ROW), lens)
+        kd = np.flatnonzero(ja == rows)
+        assert len(kd) == ROW
+        boost = 3.0 * np.sqrt(4.0 * nb * lens)
+        val.reshape(-1, nb, nb)[kd[:, None], np.arange(nb), np.arange(nb)] += boost[:, None]
+    # the edges this matrix exists for: a later edit cannot quietly lose one
+    assert lens.max() > 2 * CAPB                                   # one block row alone spans three LDS chunks
+    assert ROW % RW != 0 and ROW % (4 * RW) != 0                   # last wave tile with nbr < RW, last workgroup partial
+    tiles = ia[np.minimum(np.arange(0, ROW + RW, RW), ROW)]        # block offsets of the wave tiles
+    per_tile = np.diff(tiles)
+    assert (per_tile > CAPB).sum() >= 2                            # multi-chunk tiles at both ends
+    if not square:
+        assert (per_tile[:-1] == 0).any() and lens[RW - 1] == 0 and lens[RW] == 0   # a whole empty tile; empty rows at a tile's end and start
+    if nb % 2:
+        tail = per_tile % CAPB                                     # blocks of a tile's last chunk (0: it is a full one)
+        assert ((tail % 2 == 1) | ((per_tile >= CAPB) & (CAPB % 2 == 1))).any()     # a chunk of an odd number of doubles
+    first = np.flatnonzero(lens > 1)
+    assert all(len(set(ja[ia[i]:ia[i + 1]])) == lens[i] for i in (0, ROW - 1, int(first[0])))   # distinct columns
+    assert (np.diff(ja[ia[0]:ia[1]]) < 0).any()                    # unsorted
+    return ROW, COL, ia, ja, val, lens
+
+
+RAGGED_SHAPES = {"square": (True, 0), "wide": (False, 37), "tall": (False, -50)}   # COL = ROW, ROW + 37, ROW - 50
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_case(nb, shape):
+    """ragged_bsr(nb, .) in one of RAGGED_SHAPES with the vectors the tests share (read-only: built once per session):
+    dict(ROW, COL, nb, ia, ja, val, lens, x (COL nb), y0, b, u0 (ROW nb))."""
+    square, extra = RAGGED_SHAPES[shape]
+    seed = 100 * nb + list(RAGGED_SHAPES).index(shape)
+    ROW, COL, ia, ja, val, lens = ragged_bsr(nb, seed, square, extra)
+    rng = np.random.default_rng(seed + 7)
+    c = dict(ROW=ROW, COL=COL, nb=nb, ia=ia, ja=ja, val=val, lens=lens, x=rng.standard_normal(COL * nb),
+             y0=rng.standard_normal(ROW * nb), b=rng.standard_normal(ROW * nb), u0=rng.standard_normal(ROW * nb))
+    for v in c.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+BSR_MAXGRID = 2048   # MAXGRID of csrc/solver.hip: the largest grid launch_bsr asks for
+
+
+def wide_bsr(nb):
+    """BSR matrix of 2048 * 4 RW + 5 block rows of two blocks, the diagonal (boosted as in ragged_bsr) and column
+    (7 i + 3) mod ROW (dropped where that is the diagonal): more 4-wave tiles than the largest grid, so whatever the
+    occupancy cap is, a workgroup of k_bsr_wstream takes a second tile.  -> (ROW, COL, ia, ja, val, lens)."""
+    RW, _, _ = bsr_tile(nb)
+    ROW = BSR_MAXGRID * 4 * RW + 5
+    i = np.arange(ROW, dtype=np.int64)
+    j2 = (7 * i + 3) % ROW
+    lens = np.where(j2 == i, 1, 2)
+    ia = np.zeros(ROW + 1, dtype=np.int32)
+    ia[1:] = np.cumsum(lens)
+    ja = np.empty(int(ia[-1]), dtype=np.int32)
+    ja[ia[:-1]] = i
+    two = lens == 2
+    ja[ia[:-1][two] + 1] = j2[two]
+    val = np.random.default_rng(100 + nb).standard_normal(len(ja) * nb * nb)
+    val.reshape(-1, nb, nb)[ia[:-1, None], np.arange(nb), np.arange(nb)] += (3.0 * np.sqrt(4.0 * nb * lens))[:, None]
+    assert (ROW + 4 * RW - 1) // (4 * RW) > BSR_MAXGRID
+    return ROW, ROW, ia, ja, val, lens
+
+
+def bsr_mxv_longdouble(ROW, nb, ia, ja, val, x):
+    """y = A x and s = |A| |x| per scalar row in np.longdouble, independent of the oracle -> (y, s, m): m = products per row."""
+    NNZ = len(ja)
+    ld = np.longdouble
+    xg = x.astype(ld)[(ja.astype(np.int64) * nb)[:, None] + np.arange(nb)]          # NNZ x nb
+    prod = val.reshape(NNZ, nb, nb).astype(ld) * xg[:, None, :]                     # NNZ x nb x nb
+    y = np.zeros((ROW, nb), dtype=ld); s = np.zeros((ROW, nb), dtype=ld)
+    lens = np.diff(ia)
+    rows = np.flatnonzero(lens > 0)
+    if len(rows):
+        y[rows] = np.add.reduceat(prod.sum(axis=2), ia[:-1][rows], axis=0)
+        s[rows] = np.add.reduceat(np.abs(prod).sum(axis=2), ia[:-1][rows], axis=0)
+    return y.reshape(-1), s.reshape(-1), np.repeat(lens * nb, nb)
+
+
+def bsr_mxv_bound_ratio(ROW, nb, ia, ja, val, x, y):
+    """Worst |y - A x| / bound over the scalar rows, with the a-priori bound of any order of double-precision evaluation of
+    a row of m products, (m + 1) u / (1 - (m + 1) u) * sum |a| |x| with u = 2^-53, plus 2^-63 |y| for the 80-bit
+    evaluation it is measured against.  A ratio <= 1 passes.  Rows without blocks must be exact zeros."""
+    yl, s, m = bsr_mxv_longdouble(ROW, nb, ia, ja, val, x)
+    u = np.longdouble(2.0) ** -53
+    g = (m + 1) * u / (1 - (m + 1) * u)
+    bound = g * s + np.longdouble(2.0) ** -63 * np.abs(yl)
+    err = np.abs(y.astype(np.longdouble) - yl)
+    if np.any(err[m == 0] != 0) or not np.all(np.isfinite(y)):
+        return float("inf")
+    nz = m > 0
+    return float(np.max(err[nz] / bound[nz])) if nz.any() else 0.0
