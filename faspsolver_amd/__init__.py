@@ -58,6 +58,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_fwrapper_dbsr_krylov_ilu_",
     "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
     "fasp_hip_bsr_sweep",
+    "fasp_blas_dcsr_rap", "fasp_hip_dcsr_rap", "fasp_hip_rap_info", "fasp_hip_rap_device_count", "fasp_hip_rap_time",
 ]
 
 
@@ -252,6 +253,17 @@ def lib():
     L.fasp_hip_bsr_amg_ilu_info.argtypes = [C.c_void_p, C.c_int, T.c_double_p]
     L.fasp_hip_bsr_amg_ilu_smooth_time.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.fasp_hip_bsr_amg_ilu_smooth_time.restype = C.c_double
+    # Galerkin product on the device (csrc/rap.hip.h)
+    L.fasp_blas_dcsr_rap.argtypes = [P(T.dCSRmat), P(T.dCSRmat), P(T.dCSRmat), P(T.dCSRmat)]
+    L.fasp_blas_dcsr_rap.restype = None
+    L.fasp_hip_dcsr_rap.argtypes = L.fasp_blas_dcsr_rap.argtypes
+    L.fasp_hip_rap_info.argtypes = [P(C.c_int)]
+    L.fasp_hip_rap_device_count.argtypes = []
+    L.fasp_hip_rap_device_count.restype = C.c_long
+    L.fasp_hip_rap_time.argtypes = [P(T.dCSRmat), P(T.dCSRmat), P(T.dCSRmat), C.c_int, C.c_int]
+    L.fasp_hip_rap_time.restype = C.c_double
+    L.fasp_dcsr_free.argtypes = [P(T.dCSRmat)]
+    L.fasp_dcsr_free.restype = None
     return L
 
 
@@ -342,6 +354,42 @@ def aniso27pt(n, kx=1.0, ky=1.0, kz=0.01):
     f = np.ctypeslib.as_array(b.val, (b.row,)).copy()
     lib().fasp_hip_free_system(C.byref(A), C.byref(b), None)
     return ia, ja, a, f
+
+
+# --- Galerkin product on the device (csrc/rap.hip.h) --------------------------------
+def _rap_operands(R, A, P):
+    """R, A, P as (ia, ja, val, ncol) tuples -> the three dCSRmat structs + what keeps their arrays alive"""
+    mats, keep = [], []
+    for ia, ja, val, ncol in (R, A, P):
+        M, k = T.as_csr(ia, ja, val, ncol=ncol)
+        mats.append(M); keep.append(k)
+    return mats, keep
+
+
+def rap(R, A, P):
+    """fasp_blas_dcsr_rap (BlaSpmvCSR.c:999) on the device: R, A, P = (ia, ja, val, ncol) -> (ia, ja, val) of R A P, the
+    reference's bytes.  Raises on a status < 0 (fasp_hip_dcsr_rap)."""
+    (r, a, p), _keep = _rap_operands(R, A, P)
+    out = T.dCSRmat()
+    st = lib().fasp_hip_dcsr_rap(C.byref(r), C.byref(a), C.byref(p), C.byref(out))
+    if st < 0:
+        raise RuntimeError(f"fasp_hip_dcsr_rap failed with status {st}")
+    res = T.csr_arrays(out)
+    lib().fasp_dcsr_free(C.byref(out))
+    return res
+
+
+def rap_info():
+    """The last device product: dict(form, batches, lds, rows) (fasp_hip_rap_info)."""
+    info = (C.c_int * 4)()
+    lib().fasp_hip_rap_info(info)
+    return dict(zip(("form", "batches", "lds", "rows"), list(info)))
+
+
+def rap_time(R, A, P, where, reps=3):
+    """Seconds per product (fasp_hip_rap_time): where = 0 host, 1 device end to end, 2 device kernels alone."""
+    (r, a, p), _keep = _rap_operands(R, A, P)
+    return lib().fasp_hip_rap_time(C.byref(r), C.byref(a), C.byref(p), where, reps)
 
 
 def solver_dcsr_krylov_amg(ia, ja, a, b, x, itparam, amgparam):

@@ -158,6 +158,11 @@ int host_setup_rs(const dCSRmat* A, AMG_param* param, HostHierarchy& H);
 extern void (*g_on_level_ready)(int level, void* ctx);
 extern void (*g_on_level_matrix)(int level, void* ctx);   // classical setup: the level's A is final (P, R, cfmark are not yet); same ctx
 extern void* g_on_level_ready_ctx;
+// The Galerkin product of the setups (host_setup.cpp, galerkin_product).  host_setup.cpp knows no HIP: solver.hip sets this hook
+// (rap.hip.h).  It returns 1 when it has formed C = R A P on the device (the bytes of the host product), 0 when the host is to form it
+// (switched off, no usable device, several ranks), < 0 on an error it has reported.  galerkin_rap_host: the host product itself.
+extern int (*g_device_rap_hook)(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR& C);
+void galerkin_rap_host(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR& C);
 // Smoothed aggregation (PreAMGSetupSA.c:63: VMB aggregation, smoothed P and R).
 int host_setup_sa(const dCSRmat* A, AMG_param* param, HostHierarchy& H);
 // Unsmoothed aggregation (PreAMGSetupUA.c:55: VMB aggregation, boolean P, rap_agg).

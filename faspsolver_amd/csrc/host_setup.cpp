@@ -1366,6 +1366,18 @@ void galerkin_rap(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR&
     C.ia = std::move(cia);
 }
 
+// The Galerkin product of the three setups: the device product (rap.hip.h) where the hook takes it -- fasp_hip_tune("device_rap", 1),
+// a usable device, one rank --, else galerkin_rap above.  Both give the same bytes.
+void galerkin_product(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR& C)
+{
+    if (g_device_rap_hook) {
+        const int st = g_device_rap_hook(R, A, P, C);
+        if (st > 0) return;
+        if (st < 0) throw std::bad_alloc();   // (the hook has said why; an overflow of the 32-bit entry count is the host product's bad_alloc too)
+    }
+    galerkin_rap(R, A, P, C);
+}
+
 void copy_csr(const dCSRmat* A, HostCSR& B)
 {
     B.row = A->row; B.col = A->col; B.nnz = A->nnz;
@@ -1756,7 +1768,7 @@ int host_setup_rs(const dCSRmat* A, AMG_param* param, HostHierarchy& H)
             transpose_csr(Lv.P, Lv.R);                                 // :212
             lap("transpose");
             H.L.emplace_back();
-            galerkin_rap(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);  // :213
+            galerkin_product(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);  // :213
             lap("RAP");
             H.L[lvl].has_coarse = true;
             if (g_on_level_ready) g_on_level_ready(lvl, g_on_level_ready_ctx);   // A, P, R, cfmark of this level are final
@@ -1798,6 +1810,8 @@ void* buf_malloc(size_t bytes)
 void (*g_on_level_ready)(int level, void* ctx) = nullptr;
 void (*g_on_level_matrix)(int level, void* ctx) = nullptr;
 void* g_on_level_ready_ctx = nullptr;
+int (*g_device_rap_hook)(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR& C) = nullptr;
+void galerkin_rap_host(const HostCSR& R, const HostCSR& A, const HostCSR& P, HostCSR& C) { galerkin_rap(R, A, P, C); }
 
 int host_setup_sa(const dCSRmat* A, AMG_param* param, HostHierarchy& H)
 {
@@ -1841,7 +1855,7 @@ int host_setup_sa(const dCSRmat* A, AMG_param* param, HostHierarchy& H)
             }
             transpose_csr(Lv.P, Lv.R);
             H.L.emplace_back();
-            galerkin_rap(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);
+            galerkin_product(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);
             H.L[lvl].has_coarse = true;
             ++lvl;
         }
@@ -1970,7 +1984,7 @@ int aggregation_symmpair(const HostCSR& A0, AMG_param& param, std::vector<int>& 
             boolean_p(vert[lvl].data(), ptrA->row, num_agg, P);
             if (P.col < MIN_CDOF) break;
             transpose_csr(P, R);
-            galerkin_rap(R, *ptrA, P, Amid[lvl + 1]);
+            galerkin_product(R, *ptrA, P, Amid[lvl + 1]);
             ptrA = &Amid[lvl + 1];
         }
         ++lvl; ++dopass;
@@ -2053,7 +2067,7 @@ int host_setup_ua(const dCSRmat* A, AMG_param* param, HostHierarchy& H)
             }
             transpose_csr(Lv.P, Lv.R);
             H.L.emplace_back();
-            galerkin_rap(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);
+            galerkin_product(H.L[lvl].R, H.L[lvl].A, H.L[lvl].P, H.L[lvl + 1].A);
             H.L[lvl].has_coarse = true;
             ++lvl;
         }

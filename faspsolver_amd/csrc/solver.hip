@@ -1204,6 +1204,7 @@ precond* fasp_hip_precond_setup(dCSRmat* A, AMG_param* amgparam)
 
 #include "precond_api.hip.h"
 #include "ilu.hip.h"
+#include "rap.hip.h"
 
 void fasp_hip_precond_free(precond* pc)
 {
@@ -2180,6 +2181,9 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "rp_xcd")) g_tune.rp_xcd = value;
     else if (!std::strcmp(key, "rp_strip")) g_tune.rp_strip = value;   // coded operators of a 3-D grid: an XCD sweeps a strip of every plane (1: the square ones, 2: the transfer operators too, default) or a slab of planes (0)
     else if (!std::strcmp(key, "host_parallel_min")) g_parallel_min_nnz = value;
+    else if (!std::strcmp(key, "rap_form")) g_rap_form = value;           // Galerkin product on the device (rap.hip.h): -1 (default) by the mean work per row, 0 one lane per coarse row, 1 one wavefront per coarse row -- same bytes
+    else if (!std::strcmp(key, "rap_arena_kb")) g_rap_arena_kb = value;   // ... KiB of its table arena: rows go in batches that fit (a batch of one row always does)
+    else if (!std::strcmp(key, "device_rap")) g_device_rap = value;       // the AMG setups form their Galerkin products on the device (1) or on the host (0, default) -- same bytes; read by every product
     else if (!std::strcmp(key, "lanes")) g_tune.lanes = value;
     else if (!std::strcmp(key, "wrows")) g_tune.wrows = value;
     else if (!std::strcmp(key, "wcap")) g_tune.wcap = value;

@@ -382,6 +382,11 @@ double fasp_blas_darray_norminf(const int n, const double* x);                  
 void   fasp_blas_darray_axpy(const int n, const double a, const double* x, double* y); /* BlaArray.c:90 */
 void   fasp_blas_darray_axpby(const int n, const double a, const double* x,
                               const double b, double* y);                             /* BlaArray.c:620 */
+/* the Galerkin product RAP = R A P on the device, the reference's result byte for byte (IA, JA, val; every row starts with its
+ * diagonal slot, the other columns in discovery order).  Host arrays in and out; RAP's arrays are allocated with fasp_mem_calloc
+ * (release them with fasp_dcsr_free).  Wrong dimensions or more than 2^31 - 1 entries: prints "### ERROR: ..." and exits with the
+ * status, as fasp_chkerr does. */
+void   fasp_blas_dcsr_rap(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, dCSRmat* RAP);   /* BlaSpmvCSR.c:999 */
 /* the remaining kernel-level names of the path, host arrays in and out */
 double fasp_blas_dcsr_vmv(const dCSRmat* A, const double* x, const double* y);           /* BlaSpmvCSR.c:839  y' A x */
 void   fasp_blas_dcsr_mxv_agg(const dCSRmat* A, const double* x, double* y);             /* BlaSpmvCSR.c:438  unit entries, val unread */

@@ -62,6 +62,19 @@ int    fasp_hip_bsr_amg_get_ilu(const fasp_hip_amg_bsr* h, int level, ILU_data* 
 int    fasp_hip_bsr_amg_ilu_info(const fasp_hip_amg_bsr* h, int level, double info[6]);
 double fasp_hip_bsr_amg_ilu_smooth_time(fasp_hip_amg_bsr* h, int level, int reps);
 
+/* The Galerkin product on the device (csrc/rap.hip.h).  fasp_hip_dcsr_rap: fasp_blas_dcsr_rap with a status instead of an exit --
+ * ERROR_INPUT_PAR for NULL arguments or dimensions that do not chain (checked before anything touches a device; *RAP is all zero
+ * then), ERROR_ALLOC_MEM for a result of more than 2^31 - 1 entries, ERROR_MISC without a device.  fasp_hip_rap_info: the last
+ * product, info = {form used (0 one lane per coarse row, 1 one wavefront per coarse row; a P with a repeated column inside a row
+ * takes form 0 whatever was asked for), row batches of the table arena (the larger of the two passes), 1 when rows kept their
+ * tables in LDS, rows}.  fasp_hip_rap_device_count: products run on the device since the library was loaded.  fasp_hip_rap_time:
+ * seconds per product over `reps` products -- where = 0 the host product of the setups, 1 the device end to end (upload of the
+ * operands, kernels, download of the result; after one warm-up), 2 its kernels alone by events; < 0: error. */
+int    fasp_hip_dcsr_rap(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, dCSRmat* RAP);
+int    fasp_hip_rap_info(int info[4]);
+long   fasp_hip_rap_device_count(void);
+double fasp_hip_rap_time(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, int where, int reps);
+
 /* Run-time switches (A/B tests, profiling, and ONE behavioural mode):
  *   kernel selection / launch geometry: maxgrid, xcd, nt, kind, lanes, wrows, wcap (-1 = automatic), gen2 (0 round-1
  *     kernels, 1, 2 = default), compress (lossless matrix coding on/off), ja16, ws2_bpc, rpl, lds_tab, xcd_pat, rp_strip (coded operators
@@ -97,7 +110,10 @@ double fasp_hip_bsr_amg_ilu_smooth_time(fasp_hip_amg_bsr* h, int level, int reps
  *     three row windows), seq_partition (set before the upload, or FASP_HIP_SEQ_PARTITION=1: hierarchies with Gauss-Seidel / SOR
  *     smoothers are row-partitioned too and the ranks sweep by turns; default 0: such hierarchies keep every level whole),
  *     local_square (a rank's rows of a partitioned level coded with row-relative column offsets like the square operator, default 1;
- *     read at upload).
+ *     read at upload);
+ *   Galerkin product on the device: rap_form (-1 (default) by the mean work per coarse row, 0 one lane per row, 1 one wavefront
+ *     per row), rap_arena_kb (KiB of the table arena the rows are batched into) -- same bytes; device_rap (1: the AMG setups form
+ *     their Galerkin products on the device whenever one is usable and there is one rank; 0 (default): on the host) -- same bytes.
  * Unknown keys return ERROR_INPUT_PAR. */
 int fasp_hip_tune(const char* key, int value);
 /* Which kernel served the last coarsest-level solve of a hierarchy, and how it ended (read-only; tests).  info (8 ints) =
