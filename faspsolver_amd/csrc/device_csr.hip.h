@@ -1148,6 +1148,35 @@ static int launch_persistent(K kernel, int ntiles, CsrArgs& a, int blocks_per_cu
 // k_csr_sell (kernels4.hip.h): workgroups of 16 waves with the value table in dynamic LDS, grid = what is resident
 // (an operator that also has k_csr_xtile's lists keeps that kernel: it was selected there by measurement)
 static bool sell_active(const DevCSR& M) { return M.sell_code && g_tune.compress && g_tune.sell && g_tune.gen2 >= 2 && !(g_tune.xtile && M.lja16); }
+// Which kernel family launch_csr sends an operator to under the tune keys in force, as the codes of fasp_hip_amg_kernel_info and
+// fasp_hip_matrix_op: 0 k_csr_rows, 2 k_csr_wstream, 4 k_csr_dict8, 5 k_csr_rowpat, 6 k_csr_rowpat4, 7 k_csr_lstream, 8 k_csr_wstream2,
+// 9 k_csr_rowpat5, 10 k_csr_xtile, 11 k_csr_sell.  *matrix_bytes (may be NULL): the matrix data one pass reads (row pointers / indices /
+// values, or their coded form).
+static int kernel_family(const DevCSR& M, double* matrix_bytes)
+{
+    int k = M.kind;
+    double bytes = 12.0 * M.nnz + 4.0 * (M.row + 1.0);
+    if (M.kind == 0 && M.ja16 && g_tune.ja16) bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.jbase ? 4.0 * M.row : 0.0);   // 16-bit indices
+    if (M.code && g_tune.compress) { k = 4; bytes = 1.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.rowbase ? 4.0 * M.row : 0.0); }
+    if (M.pat && g_tune.compress) { k = 5; bytes = 2.0 * M.row + (M.rowbase ? 4.0 * M.row : 0.0) + 12.0 * M.npent; }
+    // second-generation kernels (kernels2.hip.h), same selection as launch_csr: 6 = k_csr_rowpat4, 7 = k_csr_lstream, 8 = k_csr_wstream2, 9 = k_csr_rowpat5, 10 = k_csr_xtile
+    // (fasp_hip_tune("rpl", 1 | 2) asks for k_csr_rowpat's rows-per-lane forms: the pair sweeps step aside)
+    if (k == 5 && g_tune.gen2 && M.nxrows >= 0 && !M.rowbase && g_tune.rpl <= 0) k = 6;
+    else if (k == 5 && g_tune.gen2 >= 2 && M.nxrows >= 0 && M.rowbase && g_tune.rpl <= 0 && (double)M.nnz <= 0.1 * g_tune.rp5_max * M.row) k = 9;   // k_csr_rowpat5
+    if (k == 2 && g_tune.gen2 && M.wrows == 64 && M.wcap == 512 && (double)M.nnz <= 7.6 * M.row) k = 7;
+    else if (k == 2 && g_tune.gen2 >= 2 && g_tune.xtile && M.lja16 && M.wrows == 64 && M.wcap == 512) {   // k_csr_xtile
+        k = 10;
+        bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + 4.0 * M.ntcols + 4.0 * ((M.row + 63) / 64 + 1.0);   // values + 16-bit positions + the tiles' column lists
+    }
+    else if (k == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512) {   // 11 = k_csr_sell (kernels4.hip.h): words + row lengths + slice table + value table
+        k = 11;
+        bytes = 4.0 * (double)M.sell_slots + 1.0 * M.row + 4.0 * (2.0 * M.sell_nslice + 1.0) + 8.0 * M.sell_nv;
+    }
+    else if (k == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512) k = 8;   // k_csr_wstream2
+    if (matrix_bytes) *matrix_bytes = bytes;
+    return k;
+}
+
 template <int OP>
 static int launch_sell(const DevCSR& M, CsrArgs& a)
 {

@@ -570,24 +570,8 @@ int fasp_hip_amg_kernel_info(const fasp_hip_amg* h, int level, int which, int* k
     const DevLevel& D = h->L[level];
     const DevCSR& M = which == 0 ? D.A : which == 1 ? D.P : D.R;
     if (!M.ia) return ERROR_INPUT_PAR;
-    int k = M.kind;
-    double bytes = 12.0 * M.nnz + 4.0 * (M.row + 1.0);
-    if (M.kind == 0 && M.ja16 && g_tune.ja16) bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.jbase ? 4.0 * M.row : 0.0);   // 16-bit indices
-    if (M.code && g_tune.compress) { k = 4; bytes = 1.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.rowbase ? 4.0 * M.row : 0.0); }
-    if (M.pat && g_tune.compress) { k = 5; bytes = 2.0 * M.row + (M.rowbase ? 4.0 * M.row : 0.0) + 12.0 * M.npent; }
-    // second-generation kernels (kernels2.hip.h), same selection as launch_csr: 6 = k_csr_rowpat4, 7 = k_csr_lstream, 8 = k_csr_wstream2, 9 = k_csr_rowpat5, 10 = k_csr_xtile
-    if (k == 5 && g_tune.gen2 && M.nxrows >= 0 && !M.rowbase) k = 6;
-    else if (k == 5 && g_tune.gen2 >= 2 && M.nxrows >= 0 && M.rowbase && (double)M.nnz <= 0.1 * g_tune.rp5_max * M.row) k = 9;   // k_csr_rowpat5
-    if (k == 2 && g_tune.gen2 && M.wrows == 64 && M.wcap == 512 && (double)M.nnz <= 7.6 * M.row) k = 7;
-    else if (k == 2 && g_tune.gen2 >= 2 && g_tune.xtile && M.lja16 && M.wrows == 64 && M.wcap == 512) {   // k_csr_xtile
-        k = 10;
-        bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + 4.0 * M.ntcols + 4.0 * ((M.row + 63) / 64 + 1.0);   // values + 16-bit positions + the tiles' column lists
-    }
-    else if (k == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512) {   // 11 = k_csr_sell (kernels4.hip.h): words + row lengths + slice table + value table
-        k = 11;
-        bytes = 4.0 * (double)M.sell_slots + 1.0 * M.row + 4.0 * (2.0 * M.sell_nslice + 1.0) + 8.0 * M.sell_nv;
-    }
-    else if (k == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512) k = 8;   // k_csr_wstream2
+    double bytes = 0.0;
+    const int k = kernel_family(M, &bytes);   // (device_csr.hip.h: the selection of launch_csr, shared with fasp_hip_matrix_op)
     if (kind) *kind = k;
     if (matrix_bytes) *matrix_bytes = bytes;
     return FASP_SUCCESS;
@@ -2383,7 +2367,9 @@ int fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const doubl
     if (!h || level < 0 || level >= (int)h->L.size()) return ERROR_INPUT_PAR;
     return row_op_host(h->L[level], which, op, x, b, y, y2, scalar, red);
 }
-// ... and of a matrix given on the host, uploaded the way a level's A is (coding, kernel selection, diagonal tables)
+// ... and of a matrix given on the host, uploaded the way a level's A is (coding, kernel selection, diagonal tables).  A rectangular matrix is
+// uploaded the way a transfer operator is: no diagonal tables, so ops 5 and 6 return ERROR_INPUT_PAR.  *kind_out: the family code of
+// fasp_hip_amg_kernel_info (kernel_family, device_csr.hip.h).
 int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out)
 {
     FASP_ENTRY();
@@ -2400,7 +2386,7 @@ int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* 
     }
     if (st >= 0 && (op == 5 || op == 6) && !D.diag) st = ERROR_INPUT_PAR;
     if (st >= 0) st = row_op_host(D, 0, op, x, b, y, y2, scalar, red);
-    if (kind_out) *kind_out = (D.A.kind == 2 && sell_active(D.A)) ? 11 : D.A.kind;
+    if (kind_out) *kind_out = kernel_family(D.A, nullptr);   // under the tune keys of this call: the family the operation ran on
     free_level(D);
     return st;
 }

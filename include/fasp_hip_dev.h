@@ -165,7 +165,11 @@ int  fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double
  * iterate), 6 L1-diagonal sweep (A only), 7 y = M x fused with (y, b), 8 y = M x with y2_i = scalar y_i / b_i written along (the fused first Jacobi
  * sweep of the next level).  red (may be NULL): the finished fused sum of ops 7 and 5 -- (y, b), (x_new, b); NaN where the kernel has none. */
 int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red);
-/* ... and of a matrix given on the host, uploaded the way a level's A is; *kind_out (may be NULL) = 11 when its sliced-ELL form is in use */
+/* ... and of a matrix given on the host, uploaded the way a level's A is.  *kind_out (may be NULL) = the kernel family the operation ran
+ * on, in the codes of fasp_hip_amg_kernel_info and from the same function, evaluated under the tune keys in force at the call: 4 k_csr_dict8,
+ * 5 k_csr_rowpat, 6 k_csr_rowpat4, 9 k_csr_rowpat5, 7 k_csr_lstream, 8 k_csr_wstream2, 10 k_csr_xtile, 11 k_csr_sell, 0 k_csr_rows,
+ * 2 k_csr_wstream.  A rectangular matrix (row != col) is accepted and uploaded the way a transfer operator is: it has no diagonal tables, so
+ * ops 5 and 6 return ERROR_INPUT_PAR; x then holds col values, b / y / y2 row values. */
 int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out);
 /* test entry: ONE sequential block sweep of the host matrix A (square, storage_manner 0, 1 <= nb <= 7, a diagonal block in every row) on the
  * device, through the level schedule and the per-level launches the block AMG cycle smooths with: block Gauss-Seidel (sor = 0; w unused) or

@@ -469,16 +469,32 @@ def bsr_mxv_longdouble(ROW, nb, ia, ja, val, x):
     return y.reshape(-1), s.reshape(-1), np.repeat(lens * nb, nb)
 
 
+def sum_bound_ratio(got, exact, sabs, m):
+    """Worst |got - exact| / bound over the entries of a vector whose entry i is a sum of m[i] rounded terms (products, or a
+    handful of elementwise operations on top of them) of absolute sum sabs[i], evaluated in double precision in ANY order, against its
+    np.longdouble evaluation `exact`: the a-priori bound (m + 1) u / (1 - (m + 1) u) * sabs with u = 2^-53, plus 2^-63 |exact| for the
+    80-bit side.  A ratio <= 1 passes.  Entries without terms (m == 0) must be exact; a non-finite result fails."""
+    ld = np.longdouble
+    m = np.asarray(m)
+    u = ld(2.0) ** -53
+    g = (m + 1) * u / (1 - (m + 1) * u)
+    bound = g * np.asarray(sabs, dtype=ld) + ld(2.0) ** -63 * np.abs(exact)
+    err = np.abs(np.asarray(got).astype(ld) - exact)
+    if np.any(err[m == 0] != 0) or not np.all(np.isfinite(got)):
+        return float("inf")
+    nz = (m > 0) & (err > 0)
+    return float(np.max(err[nz] / bound[nz])) if nz.any() else 0.0
+
+
+def csr_mxv_longdouble(ia, ja, val, x):
+    """y = A x and s = |A| |x| per row of a CSR matrix in np.longdouble, independent of the oracle -> (y, s, m): m = products per row."""
+    return bsr_mxv_longdouble(len(ia) - 1, 1, ia, ja, val, x)
+
+
 def bsr_mxv_bound_ratio(ROW, nb, ia, ja, val, x, y):
     """Worst |y - A x| / bound over the scalar rows, with the a-priori bound of any order of double-precision evaluation of
     a row of m products, (m + 1) u / (1 - (m + 1) u) * sum |a| |x| with u = 2^-53, plus 2^-63 |y| for the 80-bit
-    evaluation it is measured against.  A ratio <= 1 passes.  Rows without blocks must be exact zeros."""
+    evaluation it is measured against (sum_bound_ratio; nb = 1 is a CSR matrix).  A ratio <= 1 passes.  Rows without blocks
+    must be exact zeros."""
     yl, s, m = bsr_mxv_longdouble(ROW, nb, ia, ja, val, x)
-    u = np.longdouble(2.0) ** -53
-    g = (m + 1) * u / (1 - (m + 1) * u)
-    bound = g * s + np.longdouble(2.0) ** -63 * np.abs(yl)
-    err = np.abs(y.astype(np.longdouble) - yl)
-    if np.any(err[m == 0] != 0) or not np.all(np.isfinite(y)):
-        return float("inf")
-    nz = m > 0
-    return float(np.max(err[nz] / bound[nz])) if nz.any() else 0.0
+    return sum_bound_ratio(y, yl, s, m)
