@@ -1145,36 +1145,132 @@ static int launch_persistent(K kernel, int ntiles, CsrArgs& a, int blocks_per_cu
     return grid;
 }
 
-// k_csr_sell (kernels4.hip.h): workgroups of 16 waves with the value table in dynamic LDS, grid = what is resident
-// (an operator that also has k_csr_xtile's lists keeps that kernel: it was selected there by measurement)
-static bool sell_active(const DevCSR& M) { return M.sell_code && g_tune.compress && g_tune.sell && g_tune.gen2 >= 2 && !(g_tune.xtile && M.lja16); }
-// Which kernel family launch_csr sends an operator to under the tune keys in force, as the codes of fasp_hip_amg_kernel_info and
-// fasp_hip_matrix_op: 0 k_csr_rows, 2 k_csr_wstream, 4 k_csr_dict8, 5 k_csr_rowpat, 6 k_csr_rowpat4, 7 k_csr_lstream, 8 k_csr_wstream2,
-// 9 k_csr_rowpat5, 10 k_csr_xtile, 11 k_csr_sell.  *matrix_bytes (may be NULL): the matrix data one pass reads (row pointers / indices /
-// values, or their coded form).
+// The kernel ONE launch of a row operation runs.  plan_csr decides it -- the only place that does: launch_csr executes the plan, and
+// fasp_hip_amg_kernel_info, fasp_hip_matrix_op, fasp_hip_time_matrix and the (z, r) fusion of the smoother read it.  A value per
+// instantiation (but OP); the order is part of fasp_hip_csr_plan's report (fasp_hip_dev.h, tests/_csr_cases.py).
+enum CsrKernel : int {
+    CK_ROWS_2 = 0, CK_ROWS_4, CK_ROWS_8, CK_ROWS_16, CK_ROWS_32, CK_ROWS_64,               // k_csr_rows<L, OP>
+    CK_WSTREAM_64_512, CK_WSTREAM_64_1024, CK_WSTREAM_32_512, CK_WSTREAM_32_1024,           // k_csr_wstream<OP, wrows, wcap>
+    CK_ROWPAT_0_1, CK_ROWPAT_0_2, CK_ROWPAT_1_1, CK_ROWPAT_1_2, CK_ROWPAT_2_1, CK_ROWPAT_2_2,   // k_csr_rowpat<OP, T, RPL>
+    CK_DICT8_8, CK_DICT8_16, CK_DICT8_24,                                                   // k_csr_dict8<OP, U>
+    CK_ESTREAM_4, CK_ESTREAM_8, CK_ESTREAM_16, CK_ESTREAM_32,                               // k_csr_estream<L, OP>
+    CK_ROWPAT4, CK_ROWPAT5, CK_LSTREAM, CK_XTILE, CK_SELL, CK_WSTREAM2
+};
+struct CsrPlan {
+    CsrKernel kernel;
+    int    family;      // the code of fasp_hip_amg_kernel_info: 0 k_csr_rows (and k_csr_estream), 2 k_csr_wstream, 4 k_csr_dict8, 5 k_csr_rowpat,
+                        // 6 k_csr_rowpat4, 7 k_csr_lstream, 8 k_csr_wstream2, 9 k_csr_rowpat5, 10 k_csr_xtile, 11 k_csr_sell
+    int    tile_rows;   // rows of a tile (of a workgroup and step)
+    int    bpc;         // launch_persistent: blocks per CU at most (0: what is resident)
+    int    xcd_map;     // CsrArgs::xcd_map; -2: XCD strips (kernels.hip.h, tile_of) of tpp tiles per grid plane
+    int    tpp;         // 0: no strips
+    int    nt;          // CsrArgs::nt
+    bool   ja16, jbase; // the 16-bit column copy / its row bases are passed
+    bool   fused_zr;    // OP_JACOBI with a.partials set asks for the partials of (x_new, b) on the way out (the (z, r) of PCG from the last sweep
+                        // of level 0) and this kernel writes them: only those of the fast paths do
+    double bytes;       // matrix data one pass reads: row pointers / indices / values, or their coded form
+};
+// Pure: reads scalar fields of M, whether its pointers are set, and g_tune; calls nothing, dereferences nothing, changes nothing.
+// windowed: a row-window launch, or fasp_hip_tune("split_rows") in force; rows: the rows of the window (< 0: the whole operator).
+static CsrPlan plan_csr(const DevCSR& M, int op, bool windowed, bool want_partials, int rows = -1)
+{
+    CsrPlan p{};
+    int kind = M.kind;
+    if (rows < 0) rows = M.row;
+    if (M.code && g_tune.compress) kind = 4;  // dictionary-coded copy present: one byte per entry
+    if (M.pat && g_tune.compress) kind = 5;   // row-pattern-coded copy present: two bytes per row
+    if (g_tune.kind >= 0 && !(g_tune.kind == 4 && !M.code) && !(g_tune.kind == 5 && !M.pat)) kind = g_tune.kind;
+    const int lanes = g_tune.lanes > 0 ? g_tune.lanes : M.lanes, wrows = g_tune.wrows > 0 ? g_tune.wrows : M.wrows, wcap = g_tune.wcap > 0 ? g_tune.wcap : M.wcap;
+    const bool jac = op == OP_JACOBI, w64 = wrows == 64 && wcap == 512;
+    const bool lstream_ok = g_tune.gen2 && kind == 2 && w64 && (double)M.nnz <= 7.6 * M.row;  // tests c != r itself
+    // the other stream kernels take the diagonal from dpos: a Jacobi sweep that needs the c != r test keeps the row kernel
+    if (jac && kind != 0 && kind < 4 && (M.dup_diag || !M.dpos) && !lstream_ok) kind = 0;
+    p.xcd_map = g_tune.xcd;
+    // coded pair kernels: streaming hints on y / pattern ids / b where a vector does not fit the Infinity Cache beside the
+    // others anyway (P7(256): level 0 yes -- 0.546 -> 0.519 GB, 93 -> 88 us; level 1, 67 MB vectors, no: 63 -> 73 us with hints)
+    p.nt = g_tune.nt | ((g_tune.rp_stream > 0 || (g_tune.rp_stream < 0 && (size_t)M.row * 8 > (size_t)96 << 20)) ? 4 : 0);
+    p.ja16 = g_tune.ja16 && M.ja16; p.jbase = g_tune.ja16 && M.jbase;
+    if (M.jbase && kind != 0) p.ja16 = p.jbase = false;   // (a tuning knob sent a sub-wavefront operator elsewhere: only k_csr_rows adds the row base)
+    if (kind == 1 || kind == 3) kind = 0;   // (block-level stream, one workgroup per row: measured slower, retired to tools/lab/)
+    p.tile_rows = kind >= 4 ? BLOCK : kind == 2 ? 4 * wrows : BLOCK / lanes;
+    auto ntiles = [&] { return (rows + p.tile_rows - 1) / p.tile_rows; };
+    auto strips = [&] {   // where the operator knows its grid plane
+        const int rpb = p.tile_rows;
+        if (!g_tune.rp_strip || M.plane < 8 * rpb || M.plane % (8 * rpb) != 0 || ntiles() < 4 * (M.plane / rpb)) return;
+        p.xcd_map = -2; p.tpp = M.plane / rpb;
+    };
+    const double avg = M.row > 0 ? (double)M.nnz / M.row : 1.0, ptr_bytes = 4.0 * (M.row + 1.0), base_bytes = M.rowbase ? 4.0 * M.row : 0.0;
+    const bool pair = kind == 5 && M.nxrows >= 0 && g_tune.rpl <= 0;   // (fasp_hip_tune("rpl", 1 | 2) asks for k_csr_rowpat's rows-per-lane forms: the pair sweeps step aside)
+    p.bytes = kind == 5 ? 2.0 * M.row + base_bytes + 12.0 * M.npent : kind == 4 ? 1.0 * M.nnz + ptr_bytes + base_bytes : 12.0 * M.nnz + ptr_bytes;
+    if (pair && g_tune.gen2 && !M.rowbase) {
+        // square row-pattern-coded operator: scalar-pattern sweep, other rows through the wave's LDS queue (kernels2.hip.h)
+        p.kernel = CK_ROWPAT4; p.family = 6; p.tile_rows = 2 * BLOCK;
+        p.xcd_map = ntiles() >= 8 * 64 ? g_tune.rp_xcd : 16;  // slabs: x is fetched once per XCD (PMC: 0.18 GB instead of 0.45 GB per level-0 pass)
+        if (p.xcd_map == -1) strips();   // strips instead of slabs where the operator says how long a grid plane is
+        // (strips: three blocks per CU -- six planes of an XCD's strip in flight -- measured against two, four, five: level-0 t = A p
+        // 87-98 us against 95-105 with five; with four, 108)
+        p.bpc = p.xcd_map == -2 && g_tune.rp_bpc == 5 ? 3 : g_tune.rp_bpc;
+        p.fused_zr = jac && want_partials;
+    }
+    else if (pair && g_tune.gen2 >= 2 && M.rowbase && !jac && op != OP_L1DIAG && (double)M.nnz <= 0.1 * g_tune.rp5_max * M.row) {
+        // rectangular row-pattern-coded operator (R, P of the coded levels): pair-of-patterns sweep + LDS queue; no smoother instantiations.
+        // (measured on P7(256) level 0: prolongation, 1-6 entries per row, 140 -> 131 us; restriction, 7-13 entries per row,
+        // 68 -> 80 us: the sweep pays for short lists only)
+        p.kernel = CK_ROWPAT5; p.family = 9; p.tile_rows = 2 * BLOCK; p.bpc = 5;
+        p.xcd_map = ntiles() >= 8 * 64 ? -1 : 16;
+        if (g_tune.rp_strip >= 2) strips();
+    }
+    else if (kind == 5) {
+        const int rpl = g_tune.rpl > 0 ? g_tune.rpl : 1;
+        const bool lds = M.npat <= 512 && M.npent <= 2048 && g_tune.lds_tab != 0;
+        const int T = !lds ? 0 : M.npat <= 64 && M.npent <= 512 && g_tune.lds_tab != 3 ? 2 : 1;   // 2 = small table: more resident blocks
+        p.kernel = CsrKernel(CK_ROWPAT_0_1 + 2 * T + (rpl != 1)); p.family = 5; p.tile_rows = BLOCK * rpl;
+        if (g_tune.xcd_pat != 0) p.xcd_map = g_tune.xcd_pat;
+        if (g_tune.xcd_pat == 64 && g_tune.rp_strip >= 2) strips();
+    }
+    else if (kind == 4) { p.kernel = avg <= 8.5 ? CK_DICT8_8 : avg <= 20.0 ? CK_DICT8_16 : CK_DICT8_24; p.family = 4; }
+    // short rows (64 rows fit the 512-entry slab with room for ragged tiles): 16-byte staged stream, lane = row
+    else if (lstream_ok) { p.kernel = CK_LSTREAM; p.family = 7; p.bpc = 4; p.fused_zr = jac && want_partials; }
+    else if (kind == 2 && g_tune.gen2 >= 2 && w64) {
+        if (g_tune.xtile && M.lja16) {
+            // mid levels (20-60 nonzeros per row): the tile's distinct x entries staged in LDS, 16-bit column positions
+            p.kernel = CK_XTILE; p.family = 10; p.bpc = 3;
+            p.bytes = 10.0 * M.nnz + ptr_bytes + 4.0 * M.ntcols + 4.0 * ((M.row + 63) / 64 + 1.0);   // values + 16-bit positions + the tiles' column lists
+        }
+        else if (M.sell_code && g_tune.compress && g_tune.sell) {
+            // few distinct values, tiles that share too few columns for k_csr_xtile: sliced ELL (kernels4.hip.h), lane = row, 4 bytes per entry,
+            // workgroups of 16 waves (the rows' sums are k_csr_wstream2's)
+            p.kernel = CK_SELL; p.family = 11; p.tile_rows = SELL_BLOCK;
+            p.bytes = 4.0 * (double)M.sell_slots + 1.0 * M.row + 4.0 * (2.0 * M.sell_nslice + 1.0) + 8.0 * M.sell_nv;   // words + row lengths + slice table + value table
+        }
+        else { p.kernel = CK_WSTREAM2; p.family = 8; p.bpc = g_tune.ws2_bpc; }   // rows of any length: staged, prefetched stream
+        p.fused_zr = jac && want_partials;
+    }
+    else if (kind == 2) {
+        p.kernel = w64 ? CK_WSTREAM_64_512 : wrows == 64 ? CK_WSTREAM_64_1024 : wrows == 32 && wcap == 512 ? CK_WSTREAM_32_512 : CK_WSTREAM_32_1024; p.family = 2;
+    }
+    else {
+        if (p.ja16) p.bytes = 10.0 * M.nnz + ptr_bytes + (p.jbase ? 4.0 * M.row : 0.0);   // 16-bit indices
+        // long rows with 16-bit columns, whole-operator launches: the entry-parallel stream (kernels3.hip.h).  Not for the fused dot
+        // products (whichever wave completes a cut row would own its term of the sum) and not for row windows (they keep the row kernel).
+        // Where it is the faster one (cold, P7(256): profiles/r06_estream.txt): mean rows below 256 entries -- levels 3 and 4 there, 66 -> 50 and
+        // 51 -> 48 us per product; on the longer rows the two tie (both sit on the gather rate of the texture-address pipe) and the row
+        // kernel's epilogue is lighter.  fasp_hip_tune("estream", 2): wherever the tables exist (tests, A/B runs); 0: never.
+        const bool es_rule = g_tune.estream >= 2 || (g_tune.estream == 1 && (double)M.nnz < 256.0 * M.row);
+        if (M.es_tab && es_rule && p.ja16 && !windowed && op != OP_MXV_DOT && !(jac && (want_partials || M.dup_diag)))
+            // lanes per row: so that the rows a 512-entry chunk touches normally fit one pass of 64 / L rows (kernels3.hip.h)
+            p.kernel = avg >= 512.0 ? CK_ESTREAM_32 : avg >= 256.0 ? CK_ESTREAM_16 : avg >= 128.0 ? CK_ESTREAM_8 : CK_ESTREAM_4;
+        else
+            p.kernel = lanes == 2 ? CK_ROWS_2 : lanes == 4 ? CK_ROWS_4 : lanes == 8 ? CK_ROWS_8 : lanes == 16 ? CK_ROWS_16 : lanes == 32 ? CK_ROWS_32 : CK_ROWS_64;
+    }
+    return p;
+}
+// The report of fasp_hip_amg_kernel_info and fasp_hip_matrix_op: family and matrix bytes (may be NULL) of y = M x on the whole operator.
 static int kernel_family(const DevCSR& M, double* matrix_bytes)
 {
-    int k = M.kind;
-    double bytes = 12.0 * M.nnz + 4.0 * (M.row + 1.0);
-    if (M.kind == 0 && M.ja16 && g_tune.ja16) bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.jbase ? 4.0 * M.row : 0.0);   // 16-bit indices
-    if (M.code && g_tune.compress) { k = 4; bytes = 1.0 * M.nnz + 4.0 * (M.row + 1.0) + (M.rowbase ? 4.0 * M.row : 0.0); }
-    if (M.pat && g_tune.compress) { k = 5; bytes = 2.0 * M.row + (M.rowbase ? 4.0 * M.row : 0.0) + 12.0 * M.npent; }
-    // second-generation kernels (kernels2.hip.h), same selection as launch_csr: 6 = k_csr_rowpat4, 7 = k_csr_lstream, 8 = k_csr_wstream2, 9 = k_csr_rowpat5, 10 = k_csr_xtile
-    // (fasp_hip_tune("rpl", 1 | 2) asks for k_csr_rowpat's rows-per-lane forms: the pair sweeps step aside)
-    if (k == 5 && g_tune.gen2 && M.nxrows >= 0 && !M.rowbase && g_tune.rpl <= 0) k = 6;
-    else if (k == 5 && g_tune.gen2 >= 2 && M.nxrows >= 0 && M.rowbase && g_tune.rpl <= 0 && (double)M.nnz <= 0.1 * g_tune.rp5_max * M.row) k = 9;   // k_csr_rowpat5
-    if (k == 2 && g_tune.gen2 && M.wrows == 64 && M.wcap == 512 && (double)M.nnz <= 7.6 * M.row) k = 7;
-    else if (k == 2 && g_tune.gen2 >= 2 && g_tune.xtile && M.lja16 && M.wrows == 64 && M.wcap == 512) {   // k_csr_xtile
-        k = 10;
-        bytes = 10.0 * M.nnz + 4.0 * (M.row + 1.0) + 4.0 * M.ntcols + 4.0 * ((M.row + 63) / 64 + 1.0);   // values + 16-bit positions + the tiles' column lists
-    }
-    else if (k == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512) {   // 11 = k_csr_sell (kernels4.hip.h): words + row lengths + slice table + value table
-        k = 11;
-        bytes = 4.0 * (double)M.sell_slots + 1.0 * M.row + 4.0 * (2.0 * M.sell_nslice + 1.0) + 8.0 * M.sell_nv;
-    }
-    else if (k == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512) k = 8;   // k_csr_wstream2
-    if (matrix_bytes) *matrix_bytes = bytes;
-    return k;
+    const CsrPlan p = plan_csr(M, OP_MXV, false, false);
+    if (matrix_bytes) *matrix_bytes = p.bytes;
+    return p.family;
 }
 
 template <int OP>
@@ -1220,9 +1316,6 @@ static int launch_rowpat5(CsrArgs& a)
 // per-block partials written from slot goff on.  hi < 0: the whole operator.
 constexpr int WIN_ALIGN = DIST_WIN_ALIGN;
 struct RowWin { int lo = 0, hi = -1, goff = 0; };
-// OP_JACOBI with a.partials set asks for the partials of (x_new, b) on the way out (the (z, r) of PCG from the last
-// sweep of level 0).  Only the kernels of the fast paths do it; a launch that did sets this flag.
-static bool g_jacobi_dot_done = false;
 
 // numbering bridge of a transfer operator (DevCSR::bridge): gather behind a restriction -- with the next level's first Jacobi sweep from
 // the zero guess written along, zx_store's expression -- and scatter in front of a prolongation
@@ -1274,178 +1367,89 @@ static int launch_csr(const DevCSR& M0, CsrArgs a, RowWin win = RowWin())
         w.lo = hi; w.hi = M0.row; w.goff = G;
         return G + launch_csr<OP>(M0, a, w);
     }
-    DevCSR M = M0;  // shallow copy: tuning overrides
+    const DevCSR& M = M0;
     const int w_lo = win.hi >= 0 ? win.lo : 0, w_hi = win.hi >= 0 ? std::min(win.hi, M0.row) : M0.row;
     if (w_hi <= w_lo && win.hi >= 0) return 0;
     if (a.partials) a.partials += win.goff;
-    auto set_tiles = [&](int rpb) {
-        // a row window starts at a multiple of WIN_ALIGN; a kernel whose tile size does not divide it (only reachable through
-        // fasp_hip_tune: block-stream tiles beyond 1024 rows, k_csr_rowpat with 8 rows per lane) would compute rows outside
-        // the window a second time -- refuse loudly instead
-        if (win.hi >= 0 && rpb > 0 && (w_lo % rpb) != 0) {
-            std::fprintf(stderr, "### ERROR: fasp_hip: row window at %d with a kernel tile of %d rows (a tuning knob broke the window alignment)\n", w_lo, rpb);
-            std::abort();
-        }
-        a.nrow = w_hi; a.row_lo = w_lo; a.tile0 = w_lo / rpb;
-        a.ntiles = (w_hi - w_lo + rpb - 1) / rpb;
-        a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    };
-    // XCD strips (kernels.hip.h, tile_of, xcd_map == -2) for a kernel with tiles of `rpb` rows, where the operator knows its grid plane
-    auto strips = [&](int rpb) {
-        if (!g_tune.rp_strip || M.plane < 8 * rpb || M.plane % (8 * rpb) != 0 || a.ntiles < 4 * (M.plane / rpb)) return false;
-        a.xcd_map = -2; a.tpp = M.plane / rpb; a.tiles_per_xcd = a.tpp / 8;
-        return true;
-    };
-    if (M.code && g_tune.compress) M.kind = 4;  // dictionary-coded copy present: one byte per entry
-    if (M.pat && g_tune.compress) M.kind = 5;   // row-pattern-coded copy present: two bytes per row
-    if (g_tune.kind >= 0 && !(g_tune.kind == 4 && !M.code) && !(g_tune.kind == 5 && !M.pat)) M.kind = g_tune.kind;
-    if (g_tune.lanes > 0) M.lanes = g_tune.lanes;
-    if (g_tune.wrows > 0) M.wrows = g_tune.wrows;
-    if (g_tune.wcap > 0) M.wcap = g_tune.wcap;
-    const bool lstream_ok = g_tune.gen2 && M.kind == 2 && M.wrows == 64 && M.wcap == 512 && (double)M.nnz <= 7.6 * M.row;  // tests c != r itself
-    if (OP == OP_JACOBI && M.kind != 0 && M.kind < 4 && (M.dup_diag || !M.dpos) && !lstream_ok) M.kind = 0;  // needs the c != r test
-    a.xcd_map = g_tune.xcd;
-    a.nt = g_tune.nt;
-    // coded pair kernels: streaming hints on y / pattern ids / b where a vector does not fit the Infinity Cache beside the
-    // others anyway (P7(256): level 0 yes -- 0.546 -> 0.519 GB, 93 -> 88 us; level 1, 67 MB vectors, no: 63 -> 73 us with hints)
-    if (g_tune.rp_stream > 0 || (g_tune.rp_stream < 0 && (size_t)M.row * 8 > (size_t)96 << 20)) a.nt |= 4;
-    a.nrow = M.row; a.ia = M.ia; a.ja = M.ja; a.val = M.val; a.dpos = M.dpos;
-    a.ja16 = g_tune.ja16 ? M.ja16 : nullptr;
-    a.jbase = g_tune.ja16 ? M.jbase : nullptr;
-    if (M.jbase && M.kind != 0) { a.ja16 = nullptr; a.jbase = nullptr; }   // (a tuning knob sent a sub-wavefront operator elsewhere: only k_csr_rows adds the row base)
-    if (M.kind == 1 || M.kind == 3) M.kind = 0;   // (block-level stream, one workgroup per row: measured slower, retired to tools/lab/)
-    const int rpb = M.kind >= 4 ? BLOCK : M.kind == 2 ? 4 * M.wrows : BLOCK / M.lanes;
-    set_tiles(rpb);
-    if (M.kind == 5 && g_tune.gen2 && M.nxrows >= 0 && !M.rowbase && g_tune.rpl <= 0) {
-        // square row-pattern-coded operator: scalar-pattern sweep, other rows through the wave's LDS queue (kernels2.hip.h)
-        a.pat = M.pat; a.pstart = M.pstart; a.plen = M.plen; a.poff = M.poff; a.pval = M.pval;
-        a.npat = M.npat; a.npent = M.npent; a.ncol = M.col; a.rowbase = nullptr;
-        set_tiles(2 * BLOCK);
-        a.xcd_map = a.ntiles >= 8 * 64 ? g_tune.rp_xcd : 16;  // slabs: x is fetched once per XCD (PMC: 0.18 GB instead of 0.45 GB per level-0 pass)
-        // strips instead of slabs where the operator says how long a grid plane is (kernels.hip.h, tile_of)
-        if (a.xcd_map == -1) strips(2 * BLOCK);
-        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
-        // (strips: three blocks per CU -- six planes of an XCD's strip in flight -- measured against two, four, five: level-0 t = A p
-        // 87-98 us against 95-105 with five; with four, 108)
-        return launch_persistent(k_csr_rowpat4<OP>, a.ntiles, a, a.xcd_map == -2 && g_tune.rp_bpc == 5 ? 3 : g_tune.rp_bpc);
+    const CsrPlan p = plan_csr(M, OP, win.hi >= 0 || g_tune.split_rows > 0, a.partials != nullptr, w_hi - w_lo);
+    const int rpb = p.tile_rows;
+    // a row window starts at a multiple of WIN_ALIGN; a kernel whose tile size does not divide it (only reachable through
+    // fasp_hip_tune: block-stream tiles beyond 1024 rows, k_csr_rowpat with 8 rows per lane) would compute rows outside
+    // the window a second time -- refuse loudly instead
+    if (win.hi >= 0 && rpb > 0 && (w_lo % rpb) != 0) {
+        std::fprintf(stderr, "### ERROR: fasp_hip: row window at %d with a kernel tile of %d rows (a tuning knob broke the window alignment)\n", w_lo, rpb);
+        std::abort();
     }
-    // (measured on P7(256) level 0: prolongation, 1-6 entries per row, 140 -> 131 us; restriction, 7-13 entries per row,
-    // 68 -> 80 us: the sweep pays for short lists only)
-    if (M.kind == 5 && g_tune.gen2 >= 2 && M.nxrows >= 0 && M.rowbase && g_tune.rpl <= 0 && OP != OP_JACOBI && OP != OP_L1DIAG &&
-        (double)M.nnz <= 0.1 * g_tune.rp5_max * M.row) {
-        // rectangular row-pattern-coded operator (R, P of the coded levels): pair-of-patterns sweep + LDS queue
-        a.pat = M.pat; a.pstart = M.pstart; a.plen = M.plen; a.poff = M.poff; a.pval = M.pval;
-        a.npat = M.npat; a.npent = M.npent; a.ncol = M.col; a.rowbase = M.rowbase;
-        set_tiles(2 * BLOCK);
-        a.xcd_map = a.ntiles >= 8 * 64 ? -1 : 16;
-        if (g_tune.rp_strip >= 2) strips(2 * BLOCK);
-        return launch_rowpat5<OP>(a);
+    a.nrow = w_hi; a.row_lo = w_lo; a.tile0 = w_lo / rpb;
+    a.ntiles = (w_hi - w_lo + rpb - 1) / rpb; a.tiles_per_xcd = (a.ntiles + 7) / 8;
+    a.xcd_map = p.xcd_map; a.nt = p.nt;
+    if (p.tpp) { a.tpp = p.tpp; a.tiles_per_xcd = p.tpp / 8; }
+    a.ia = M.ia; a.ja = M.ja; a.val = M.val; a.dpos = M.dpos;
+    a.ja16 = p.ja16 ? M.ja16 : nullptr; a.jbase = p.jbase ? M.jbase : nullptr;
+    // what the kernel's family reads beyond that (k_csr_sell: launch_sell)
+    if (p.family == 5 || p.family == 6 || p.family == 9) {
+        a.pat = M.pat; a.pstart = M.pstart; a.plen = M.plen; a.poff = M.poff; a.pval = M.pval; a.rowbase = M.rowbase;
+        a.npat = M.npat; a.npent = M.npent; a.ncol = M.col;
     }
-    if (M.kind == 5) {
-        a.pat = M.pat; a.pstart = M.pstart; a.poff = M.poff; a.pval = M.pval; a.rowbase = M.rowbase;
-        a.npat = M.npat; a.npent = M.npent;
-        const double avg = M.row > 0 ? (double)M.nnz / M.row : 1.0;
-        const bool lds = M.npat <= 512 && M.npent <= 2048 && g_tune.lds_tab != 0;
-        const int rpl = g_tune.rpl > 0 ? g_tune.rpl : 1;
-        a.plen = M.plen; a.ncol = M.col;
-        if (g_tune.xcd_pat != 0) a.xcd_map = g_tune.xcd_pat;
-        set_tiles(BLOCK * rpl);
-        if (g_tune.xcd_pat == 64 && g_tune.rp_strip >= 2) strips(BLOCK * rpl);
-        (void)avg;
-        if (lds && M.npat <= 64 && M.npent <= 512 && g_tune.lds_tab != 3) {  // small table: more resident blocks
-            if (rpl == 1) return launch_persistent(k_csr_rowpat<OP, 2, 1>, a.ntiles, a);
-            return launch_persistent(k_csr_rowpat<OP, 2, 2>, a.ntiles, a);
-        }
-        if (lds) {
-            if (rpl == 1) return launch_persistent(k_csr_rowpat<OP, 1, 1>, a.ntiles, a);
-            return launch_persistent(k_csr_rowpat<OP, 1, 2>, a.ntiles, a);
-        }
-        if (rpl == 1) return launch_persistent(k_csr_rowpat<OP, 0, 1>, a.ntiles, a);
-        return launch_persistent(k_csr_rowpat<OP, 0, 2>, a.ntiles, a);
+    if (p.family == 4) { a.code = M.code; a.rowbase = M.rowbase; a.doff = M.doff; a.dval = M.dval; }
+    if (p.kernel == CK_XTILE) { a.lja16 = M.lja16; a.tptr = M.tptr; a.tcols = M.tcols; }
+#define PERSIST(...) return launch_persistent(__VA_ARGS__, a.ntiles, a, p.bpc)
+    switch (p.kernel) {
+        case CK_ROWS_2:  PERSIST(k_csr_rows<2, OP>);
+        case CK_ROWS_4:  PERSIST(k_csr_rows<4, OP>);
+        case CK_ROWS_8:  PERSIST(k_csr_rows<8, OP>);
+        case CK_ROWS_16: PERSIST(k_csr_rows<16, OP>);
+        case CK_ROWS_32: PERSIST(k_csr_rows<32, OP>);
+        case CK_ROWS_64: PERSIST(k_csr_rows<64, OP>);
+        case CK_WSTREAM_64_512:  PERSIST(k_csr_wstream<OP, 64, 512>);
+        case CK_WSTREAM_64_1024: PERSIST(k_csr_wstream<OP, 64, 1024>);
+        case CK_WSTREAM_32_512:  PERSIST(k_csr_wstream<OP, 32, 512>);
+        case CK_WSTREAM_32_1024: PERSIST(k_csr_wstream<OP, 32, 1024>);
+        case CK_ROWPAT_0_1: PERSIST(k_csr_rowpat<OP, 0, 1>);
+        case CK_ROWPAT_0_2: PERSIST(k_csr_rowpat<OP, 0, 2>);
+        case CK_ROWPAT_1_1: PERSIST(k_csr_rowpat<OP, 1, 1>);
+        case CK_ROWPAT_1_2: PERSIST(k_csr_rowpat<OP, 1, 2>);
+        case CK_ROWPAT_2_1: PERSIST(k_csr_rowpat<OP, 2, 1>);
+        case CK_ROWPAT_2_2: PERSIST(k_csr_rowpat<OP, 2, 2>);
+        case CK_DICT8_8:  PERSIST(k_csr_dict8<OP, 8>);
+        case CK_DICT8_16: PERSIST(k_csr_dict8<OP, 16>);
+        case CK_DICT8_24: PERSIST(k_csr_dict8<OP, 24>);
+        case CK_ROWPAT4:  PERSIST(k_csr_rowpat4<OP>);
+        case CK_ROWPAT5:  return launch_rowpat5<OP>(a);
+        case CK_LSTREAM:  PERSIST(k_csr_lstream<OP, 512>);
+        case CK_XTILE:    PERSIST(k_csr_xtile<OP>);
+        case CK_SELL:     return launch_sell<OP>(M, a);
+        case CK_WSTREAM2: PERSIST(k_csr_wstream2<OP>);
+        default: break;   // k_csr_estream<L, OP>
     }
-    if (M.kind == 4) {
-        a.code = M.code; a.rowbase = M.rowbase; a.doff = M.doff; a.dval = M.dval;
-        const double avg = M.row > 0 ? (double)M.nnz / M.row : 1.0;
-        if (avg <= 8.5) return launch_persistent(k_csr_dict8<OP, 8>, a.ntiles, a);
-        if (avg <= 20.0) return launch_persistent(k_csr_dict8<OP, 16>, a.ntiles, a);
-        return launch_persistent(k_csr_dict8<OP, 24>, a.ntiles, a);
-    }
-    if (M.kind == 2 && g_tune.gen2 && M.wrows == 64 && M.wcap == 512 && (double)M.nnz <= 7.6 * M.row) {
-        // short rows (64 rows fit the 512-entry slab with room for ragged tiles): 16-byte staged stream, lane = row
-        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
-        return launch_persistent(k_csr_lstream<OP, 512>, a.ntiles, a, 4);
-    }
-    if (M.kind == 2 && g_tune.gen2 >= 2 && g_tune.xtile && M.lja16 && M.wrows == 64 && M.wcap == 512 && (OP != OP_JACOBI || (M.dpos && !M.dup_diag)))
-    {
-        // mid levels (20-60 nonzeros per row): the tile's distinct x entries staged in LDS, 16-bit column positions
-        a.lja16 = M.lja16; a.tptr = M.tptr; a.tcols = M.tcols;
-        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
-        return launch_persistent(k_csr_xtile<OP>, a.ntiles, a, 3);
-    }
-    if (M.kind == 2 && sell_active(M) && M.wrows == 64 && M.wcap == 512 && (OP != OP_JACOBI || (M.dpos && !M.dup_diag))) {
-        // mid-length rows, few distinct values, tiles that share too few columns for k_csr_xtile: sliced ELL, lane = row, 4 bytes per entry
-        // (the rows' sums are k_csr_wstream2's)
-        set_tiles(SELL_BLOCK);
-        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
-        return launch_sell<OP>(M, a);
-    }
-    if (M.kind == 2 && g_tune.gen2 >= 2 && M.wrows == 64 && M.wcap == 512 && (OP != OP_JACOBI || (M.dpos && !M.dup_diag)))
-    {
-        if (OP == OP_JACOBI && a.partials) g_jacobi_dot_done = true;
-        return launch_persistent(k_csr_wstream2<OP>, a.ntiles, a, g_tune.ws2_bpc);   // rows of any length: staged, prefetched stream
-    }
-    if (M.kind == 2) {
-        if (M.wrows == 64 && M.wcap == 512) return launch_persistent(k_csr_wstream<OP, 64, 512>, a.ntiles, a);
-        if (M.wrows == 64) return launch_persistent(k_csr_wstream<OP, 64, 1024>, a.ntiles, a);
-        if (M.wrows == 32 && M.wcap == 512) return launch_persistent(k_csr_wstream<OP, 32, 512>, a.ntiles, a);
-        return launch_persistent(k_csr_wstream<OP, 32, 1024>, a.ntiles, a);
-    }
-    // long rows with 16-bit columns, whole-operator launches: the entry-parallel stream (kernels3.hip.h).  Not for the fused dot
-    // products (whichever wave completes a cut row would own its term of the sum) and not for row windows (they keep the row kernel).
-    // Where it is the faster one (cold, P7(256): profiles/r06_estream.txt): mean rows below 256 entries -- levels 3 and 4 there, 66 -> 50 and
-    // 51 -> 48 us per product; on the longer rows the two tie (both sit on the gather rate of the texture-address pipe) and the row
-    // kernel's epilogue is lighter.  fasp_hip_tune("estream", 2): wherever the tables exist (tests, A/B runs); 0: never.
-    const bool es_rule = g_tune.estream >= 2 || (g_tune.estream == 1 && (double)M.nnz < 256.0 * M.row);
-    if (M.es_tab && es_rule && a.ja16 && win.hi < 0 && g_tune.split_rows <= 0 && OP != OP_MXV_DOT && !(OP == OP_JACOBI && (a.partials || M.dup_diag))) {
-        const int W = M.es_W, nc = M.es_nc;
-        a.es_wc = M.es_tab; a.es_centry = a.es_wc + W + 1; a.es_crow = a.es_centry + nc + 1; a.es_hw0 = a.es_crow + nc + 1; a.es_np = a.es_hw0 + W;
-        a.es_part = M.es_part; a.es_cnt = reinterpret_cast<unsigned*>(M.es_part + 2 * (size_t)W);
-        a.es_cbase = M.es_ja16 ? a.es_np + W : nullptr; a.es_ja16 = M.es_ja16;
-        // lanes per row: so that the rows a 512-entry chunk touches normally fit one pass of 64 / L rows (kernels3.hip.h)
-        const double avg = M.row > 0 ? (double)M.nnz / M.row : 1.0;
-        const int lanes = avg >= 512.0 ? 32 : avg >= 256.0 ? 16 : avg >= 128.0 ? 8 : 4;
-        static bool attr_set = false;
+#undef PERSIST
+    const int W = M.es_W, nc = M.es_nc, lanes = 4 << (p.kernel - CK_ESTREAM_4);
+    a.es_wc = M.es_tab; a.es_centry = a.es_wc + W + 1; a.es_crow = a.es_centry + nc + 1; a.es_hw0 = a.es_crow + nc + 1; a.es_np = a.es_hw0 + W;
+    a.es_part = M.es_part; a.es_cnt = reinterpret_cast<unsigned*>(M.es_part + 2 * (size_t)W);
+    a.es_cbase = M.es_ja16 ? a.es_np + W : nullptr; a.es_ja16 = M.es_ja16;
+    static bool attr_set = false;
 #define ES_ATTR(LL) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_csr_estream<LL, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, ES_LDS_BYTES)
-        if (!attr_set) { ES_ATTR(32); ES_ATTR(16); ES_ATTR(8); ES_ATTR(4); attr_set = true; }
+    if (!attr_set) { ES_ATTR(32); ES_ATTR(16); ES_ATTR(8); ES_ATTR(4); attr_set = true; }
 #undef ES_ATTR
 #define ES_LAUNCH(LL) hipLaunchKernelGGL((k_csr_estream<LL, OP>), dim3(W / 4), dim3(BLOCK), ES_LDS_BYTES, g_ctx.stream, a)
 #ifdef FASP_LAB_DEBUG
-        if (OP == OP_MXV && g_tune.es_dbg) {   // (tools/lab: which part of the kernel costs what)
+    if (OP == OP_MXV && g_tune.es_dbg) {   // (tools/lab: which part of the kernel costs what)
 #define ES_DBG(LL, DD) do { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_csr_estream<LL, OP_MXV, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, ES_LDS_BYTES); hipLaunchKernelGGL((k_csr_estream<LL, OP_MXV, DD>), dim3(W / 4), dim3(BLOCK), ES_LDS_BYTES, g_ctx.stream, a); } while (0)
-            const int dd = g_tune.es_dbg;
-            if (lanes == 32) { if (dd == 1) ES_DBG(32, 1); else if (dd == 2) ES_DBG(32, 2); else if (dd == 3) ES_DBG(32, 3); else if (dd == 4) ES_DBG(32, 4); else ES_DBG(32, 7); }
-            else if (lanes == 16) { if (dd == 1) ES_DBG(16, 1); else if (dd == 2) ES_DBG(16, 2); else if (dd == 3) ES_DBG(16, 3); else if (dd == 4) ES_DBG(16, 4); else ES_DBG(16, 7); }
-            else if (lanes == 8) { if (dd == 1) ES_DBG(8, 1); else if (dd == 2) ES_DBG(8, 2); else if (dd == 3) ES_DBG(8, 3); else if (dd == 4) ES_DBG(8, 4); else ES_DBG(8, 7); }
-            else { if (dd == 1) ES_DBG(4, 1); else if (dd == 2) ES_DBG(4, 2); else if (dd == 3) ES_DBG(4, 3); else if (dd == 4) ES_DBG(4, 4); else ES_DBG(4, 7); }
+        const int dd = g_tune.es_dbg;
+        if (lanes == 32) { if (dd == 1) ES_DBG(32, 1); else if (dd == 2) ES_DBG(32, 2); else if (dd == 3) ES_DBG(32, 3); else if (dd == 4) ES_DBG(32, 4); else ES_DBG(32, 7); }
+        else if (lanes == 16) { if (dd == 1) ES_DBG(16, 1); else if (dd == 2) ES_DBG(16, 2); else if (dd == 3) ES_DBG(16, 3); else if (dd == 4) ES_DBG(16, 4); else ES_DBG(16, 7); }
+        else if (lanes == 8) { if (dd == 1) ES_DBG(8, 1); else if (dd == 2) ES_DBG(8, 2); else if (dd == 3) ES_DBG(8, 3); else if (dd == 4) ES_DBG(8, 4); else ES_DBG(8, 7); }
+        else { if (dd == 1) ES_DBG(4, 1); else if (dd == 2) ES_DBG(4, 2); else if (dd == 3) ES_DBG(4, 3); else if (dd == 4) ES_DBG(4, 4); else ES_DBG(4, 7); }
 #undef ES_DBG
-            return W / 4;
-        }
-#endif
-        static const bool es_log = std::getenv("FASP_HIP_ES_LOG") != nullptr;   // (debugging: every launch announced and waited for)
-        if (es_log) { std::fprintf(stderr, "[es rank %d] op %d rows %d cols %d nnz %d W %d chunks %d lanes %d rel %d x %p y %p b %p\n", comm_rank(), (int)OP, M.row, M.col, M.nnz, W, nc, lanes, M.es_ja16 != nullptr, (const void*)a.x, (void*)a.y, (const void*)a.b); std::fflush(stderr); }
-        if (lanes == 32) ES_LAUNCH(32); else if (lanes == 16) ES_LAUNCH(16); else if (lanes == 8) ES_LAUNCH(8); else ES_LAUNCH(4);
-#undef ES_LAUNCH
-        if (es_log) { const hipError_t e = hipStreamSynchronize(g_ctx.stream); std::fprintf(stderr, "[es rank %d] done: %s\n", comm_rank(), hipGetErrorString(e)); std::fflush(stderr); }
         return W / 4;
     }
-    switch (M.lanes) {
-        case 2:  return launch_persistent(k_csr_rows<2, OP>, a.ntiles, a);
-        case 4:  return launch_persistent(k_csr_rows<4, OP>, a.ntiles, a);
-        case 8:  return launch_persistent(k_csr_rows<8, OP>, a.ntiles, a);
-        case 16: return launch_persistent(k_csr_rows<16, OP>, a.ntiles, a);
-        case 32: return launch_persistent(k_csr_rows<32, OP>, a.ntiles, a);
-        default: return launch_persistent(k_csr_rows<64, OP>, a.ntiles, a);
-    }
+#endif
+    static const bool es_log = std::getenv("FASP_HIP_ES_LOG") != nullptr;   // (debugging: every launch announced and waited for)
+    if (es_log) { std::fprintf(stderr, "[es rank %d] op %d rows %d cols %d nnz %d W %d chunks %d lanes %d rel %d x %p y %p b %p\n", comm_rank(), (int)OP, M.row, M.col, M.nnz, W, nc, lanes, M.es_ja16 != nullptr, (const void*)a.x, (void*)a.y, (const void*)a.b); std::fflush(stderr); }
+    if (lanes == 32) ES_LAUNCH(32); else if (lanes == 16) ES_LAUNCH(16); else if (lanes == 8) ES_LAUNCH(8); else ES_LAUNCH(4);
+#undef ES_LAUNCH
+    if (es_log) { const hipError_t e = hipStreamSynchronize(g_ctx.stream); std::fprintf(stderr, "[es rank %d] done: %s\n", comm_rank(), hipGetErrorString(e)); std::fflush(stderr); }
+    return W / 4;
 }
 
 // y = A x

@@ -571,7 +571,7 @@ int fasp_hip_amg_kernel_info(const fasp_hip_amg* h, int level, int which, int* k
     const DevCSR& M = which == 0 ? D.A : which == 1 ? D.P : D.R;
     if (!M.ia) return ERROR_INPUT_PAR;
     double bytes = 0.0;
-    const int k = kernel_family(M, &bytes);   // (device_csr.hip.h: the selection of launch_csr, shared with fasp_hip_matrix_op)
+    const int k = kernel_family(M, &bytes);   // (device_csr.hip.h: plan_csr, the plan launch_csr executes)
     if (kind) *kind = k;
     if (matrix_bytes) *matrix_bytes = bytes;
     return FASP_SUCCESS;
@@ -2194,6 +2194,28 @@ int fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double*
     return FASP_SUCCESS;
 }
 
+// CPU test entry: plan_csr (device_csr.hip.h) for an operator with these traits (fasp_hip_dev.h has the layout).  No device: the plan
+// dereferences nothing, so a pointer that is "set" points at a dummy.
+int fasp_hip_csr_plan(const int* traits, int op, int windowed, int want_partials, int* plan, double* bytes)
+{
+    FASP_ENTRY();
+    if (!traits || !plan || op < OP_MXV || op > OP_MXV_DOT) return ERROR_INPUT_PAR;
+    static double dummy[1];
+    const int* t = traits;
+    auto flag = [&](int i) -> void* { return t[i] ? dummy : nullptr; };
+    DevCSR M;
+    M.row = t[0]; M.col = t[1]; M.nnz = t[2]; M.kind = t[3]; M.lanes = t[4]; M.wrows = t[5]; M.wcap = t[6]; M.nxrows = t[7]; M.plane = t[8];
+    M.npat = t[9]; M.npent = t[10]; M.sell_nv = t[11]; M.sell_nslice = t[12]; M.sell_slots = t[13]; M.ntcols = t[14]; M.es_W = t[15]; M.es_nc = t[16];
+    M.code = (unsigned char*)flag(17); M.pat = (unsigned short*)flag(18); M.rowbase = (int*)flag(19); M.dpos = (int*)flag(20); M.dup_diag = t[21] != 0;
+    M.ja16 = (unsigned short*)flag(22); M.jbase = (int*)flag(23); M.lja16 = (unsigned short*)flag(24); M.sell_code = (unsigned*)flag(25);
+    M.es_tab = (int*)flag(26); M.es_ja16 = (unsigned short*)flag(27);
+    const CsrPlan p = plan_csr(M, op, windowed || g_tune.split_rows > 0, want_partials != 0);
+    const int out[11] = {(int)p.kernel, p.family, p.tile_rows, p.bpc, p.xcd_map, p.tpp, p.nt, p.ja16, p.jbase, p.fused_zr, kernel_family(M, nullptr)};
+    std::copy(out, out + 11, plan);
+    if (bytes) *bytes = p.bytes;
+    return FASP_SUCCESS;
+}
+
 // CPU test entry: the tables of k_csr_estream for a matrix with these row pointers, walked on the host (device_csr.hip.h)
 int fasp_hip_estream_selftest(const int* ia, int nrow, int nnz, int per_wave, int wmax, int* info)
 {
@@ -2337,10 +2359,9 @@ static int row_op_host(DevLevel& D, int which, int op, const double* x, const do
             case 4: a.alpha = scalar; G = launch_csr<OP_AXPY>(M, a); break;
             case 5:
                 a.diag = D.diag; a.omega = scalar;
-                if (red) { a.partials = g_ctx.d_partials; g_jacobi_dot_done = false; }
+                if (red) a.partials = g_ctx.d_partials;
                 G = launch_csr<OP_JACOBI>(M, a);
-                have_red = red && g_jacobi_dot_done;
-                g_jacobi_dot_done = false;
+                have_red = red && plan_csr(M, OP_JACOBI, false, true).fused_zr;
                 break;
             case 6: a.diag = D.l1; a.omega = scalar; G = launch_csr<OP_L1DIAG>(M, a); break;
             case 7: a.b = nullptr; a.dotv = db; a.partials = g_ctx.d_partials; G = launch_csr<OP_MXV_DOT>(M, a); have_red = red != nullptr; break;
@@ -2369,7 +2390,7 @@ int fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const doubl
 }
 // ... and of a matrix given on the host, uploaded the way a level's A is (coding, kernel selection, diagonal tables).  A rectangular matrix is
 // uploaded the way a transfer operator is: no diagonal tables, so ops 5 and 6 return ERROR_INPUT_PAR.  *kind_out: the family code of
-// fasp_hip_amg_kernel_info (kernel_family, device_csr.hip.h).
+// fasp_hip_amg_kernel_info (kernel_family, device_csr.hip.h: the plan of y = M x on the whole operator).
 int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out)
 {
     FASP_ENTRY();
@@ -2386,14 +2407,15 @@ int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* 
     }
     if (st >= 0 && (op == 5 || op == 6) && !D.diag) st = ERROR_INPUT_PAR;
     if (st >= 0) st = row_op_host(D, 0, op, x, b, y, y2, scalar, red);
-    if (kind_out) *kind_out = kernel_family(D.A, nullptr);   // under the tune keys of this call: the family the operation ran on
+    if (kind_out) *kind_out = kernel_family(D.A, nullptr);   // under the tune keys of this call: the family of y = M x on the whole operator
     free_level(D);
     return st;
 }
 
 // Development / test entry: one operator through the resident upload path (lossless coding, kernel selection as for a
 // hierarchy level) timed with HIP events on the launch stream.  op: 0 y = A x, 1 y -= A x, 2 Jacobi sweep, 5 y = A x
-// fused with (y, x).  Returns milliseconds per launch (< 0: error); *kind_out = kernel family as fasp_hip_amg_kernel_info.
+// fused with (y, x).  Returns milliseconds per launch (< 0: error); *kind_out = the family (codes of fasp_hip_amg_kernel_info) of
+// the plan of the operation that was timed.
 double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out)
 {
     FASP_ENTRY();
@@ -2415,11 +2437,12 @@ double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out)
     (void)hipMemsetAsync(y, 0, 8 * (size_t)n, g_ctx.stream);
     (void)hipMemsetAsync(w, 0, 8 * (size_t)n, g_ctx.stream);
     hipLaunchKernelGGL(k_set, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, 1.0, dg);
+    const int row_op = op == 0 ? OP_MXV : op == 1 ? OP_SUB : op == 2 ? OP_JACOBI : OP_MXV_DOT;
     auto run = [&]() {
-        switch (op) {
-            case 0: d_mxv(D, x, y); break;
-            case 1: d_aAxpy(-1.0, D, x, y); break;
-            case 2: { CsrArgs a{}; a.x = x; a.y = y; a.b = w; a.diag = dg; a.omega = 0.6667; launch_csr<OP_JACOBI>(D, a); } break;
+        switch (row_op) {
+            case OP_MXV: d_mxv(D, x, y); break;
+            case OP_SUB: d_aAxpy(-1.0, D, x, y); break;
+            case OP_JACOBI: { CsrArgs a{}; a.x = x; a.y = y; a.b = w; a.diag = dg; a.omega = 0.6667; launch_csr<OP_JACOBI>(D, a); } break;
             default: { CsrArgs a{}; a.x = x; a.y = y; a.dotv = x; a.partials = g_ctx.d_partials; launch_csr<OP_MXV_DOT>(D, a); } break;
         }
     };
@@ -2433,13 +2456,7 @@ double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out)
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (kind_out) {
-        int k = D.kind;
-        if (D.code && g_tune.compress) k = 4;
-        if (D.pat && g_tune.compress) k = (D.nxrows >= 0 && g_tune.gen2) ? (D.rowbase ? 9 : 6) : 5;
-        if (k == 2 && sell_active(D) && (double)D.nnz > 7.6 * D.row) k = 11;
-        *kind_out = k;
-    }
+    if (kind_out) *kind_out = plan_csr(D, row_op, g_tune.split_rows > 0, false).family;
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(w); (void)hipFree(dg);
     D.release();
     return (double)ms / reps;

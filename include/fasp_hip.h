@@ -501,10 +501,10 @@ int fasp_hip_amg_num_levels(const fasp_hip_amg* h);
 /* host-only round-trip check of the lossless matrix coding applied at upload:
  * *kind = 5 row-pattern coded, 4 byte-dictionary coded, 0 stays plain CSR; returns 0 if exact */
 int  fasp_hip_coding_selftest(const dCSRmat* A, int* kind);
-/* kernel family of operator `which` (0 A, 1 P, 2 R) on a level -- 0: sub-wavefront per row, 2: wave-level
- * stream, 4: byte-dictionary coded, 5: row-pattern coded (6, 9: its pair sweeps for square and rectangular operators),
- * 7, 8, 10, 11: the second-generation plain kernels (fasp_hip_dev.h lists them) -- and the matrix bytes one pass of it
- * reads; evaluated under the tune keys in force, by the function fasp_hip_matrix_op (fasp_hip_dev.h) reports with */
+/* kernel family that serves y = M x on operator `which` (0 A, 1 P, 2 R) of a level -- 0: sub-wavefront per row (or its
+ * entry-parallel form), 2: wave-level stream, 4: byte-dictionary coded, 5: row-pattern coded (6, 9: its pair sweeps for square
+ * and rectangular operators), 7, 8, 10, 11: the second-generation plain kernels (fasp_hip_dev.h lists them) -- and the matrix
+ * bytes one pass of it reads; evaluated under the tune keys in force, from the plan the launch itself executes */
 int  fasp_hip_amg_kernel_info(const fasp_hip_amg* h, int level, int which, int* kind, double* matrix_bytes);
 /* which: 0 = A_l, 1 = P_l, 2 = R_l.  Returns host views owned by the handle. */
 int fasp_hip_amg_get_matrix(const fasp_hip_amg* h, int level, int which, dCSRmat* view);

@@ -17,7 +17,8 @@ extern "C" {
  * with HIP events on the launch stream.  kind: 0 = SpMV, 1 = aAxpy(-1),
  * 2 = Jacobi sweep, 3 = dot, 4 = axpy. */
 double fasp_hip_time_kernel(fasp_hip_amg* h, int kind, int level, int reps);
-/* development / test entry: one operator through the resident upload path (coding + kernel selection), ms per launch */
+/* development / test entry: one operator through the resident upload path (coding + kernel selection), ms per launch; op: 0 y = A x, 1 y -= A x,
+ * 2 Jacobi sweep, else y = A x fused with (y, x); *kind_out (may be NULL) = the family of the plan of the operation that was timed */
 double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out);
 /* test entry (host only, no GPU): build the sweep schedule of the rows seq[0..ns) of A (csrc/seq_sched.cpp) and walk it on the host as the
  * device kernels do, against the plain sequential Gauss-Seidel sweep: largest deviation relative to the largest entry; < 0: error
@@ -153,6 +154,19 @@ int fasp_hip_dist_get_list(const fasp_hip_amg* h, int level, int which, ivector*
  * kernel walks them: 0 when every entry is covered once and every row is finished exactly once, else the negative number of the check
  * that failed.  info (may be NULL) = {wave ranges, chunks, rows cut by a wave boundary}.  No GPU needed. */
 int  fasp_hip_estream_selftest(const int* ia, int nrow, int nnz, int per_wave, int wmax, int* info);
+/* The kernel plan of ONE launch of a row operation (csrc/device_csr.hip.h, plan_csr: the function launch_csr executes and every report below
+ * reads) for an operator with the given traits, under the tune keys in force.  No GPU needed: the plan reads sizes and whether pointers are
+ * set, never what they point at.  traits (28 ints) = {row, col, nnz, kind, lanes, wrows, wcap, nxrows, plane, npat, npent, sell_nv, sell_nslice,
+ * sell_slots, ntcols, es_W, es_nc, then 0 / 1 for: code, pat, rowbase, dpos, dup_diag, ja16, jbase, lja16, sell_code, es_tab, es_ja16} (the fields
+ * of DevCSR).  op: the RowOp codes 0 .. 7 of fasp_hip_level_op; windowed: a row-window launch (fasp_hip_tune("split_rows") in force counts as
+ * one); want_partials: the launch passes a partials array.  plan (11 ints) = {kernel -- 0 .. 5 k_csr_rows<L> L = 2, 4, 8, 16, 32, 64; 6 .. 9
+ * k_csr_wstream<wrows, wcap> (64, 512), (64, 1024), (32, 512), (32, 1024); 10 .. 15 k_csr_rowpat<T, RPL> (0, 1), (0, 2), (1, 1), (1, 2), (2, 1),
+ * (2, 2); 16 .. 18 k_csr_dict8<U> U = 8, 16, 24; 19 .. 22 k_csr_estream<L> L = 4, 8, 16, 32; 23 k_csr_rowpat4, 24 k_csr_rowpat5, 25 k_csr_lstream,
+ * 26 k_csr_xtile, 27 k_csr_sell, 28 k_csr_wstream2 --, family (the codes of fasp_hip_amg_kernel_info; k_csr_estream counts under 0), rows of a
+ * tile, blocks per CU at most (0: what is resident), xcd_map (-2: XCD strips), tiles per grid plane of the strips (0: none), nt bits, ja16
+ * passed, jbase passed, the launch writes the fused (x_new, b) partials of a Jacobi sweep, the family fasp_hip_amg_kernel_info reports for the
+ * operator (that of op 0 on the whole operator)}; *bytes (may be NULL) = matrix bytes of one pass. */
+int  fasp_hip_csr_plan(const int* traits, int op, int windowed, int want_partials, int* plan, double* bytes);
 /* The value-indexed sliced-ELL coding of k_csr_sell (csrc/kernels4.hip.h) built on the HOST as an upload would build it.  cap_percent: largest
  * slots / entries accepted, in percent (<= 0: the product's 125).  info[8] = {coded (1 / 0), why not (0 coded, 1 size or mean row length outside the
  * range served, 2 a row beyond 255 entries, 3 padding over the cap, 4 too many distinct values, 5 index + offset beyond 32 bits), distinct values,
@@ -165,10 +179,11 @@ int  fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double
  * iterate), 6 L1-diagonal sweep (A only), 7 y = M x fused with (y, b), 8 y = M x with y2_i = scalar y_i / b_i written along (the fused first Jacobi
  * sweep of the next level).  red (may be NULL): the finished fused sum of ops 7 and 5 -- (y, b), (x_new, b); NaN where the kernel has none. */
 int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red);
-/* ... and of a matrix given on the host, uploaded the way a level's A is.  *kind_out (may be NULL) = the kernel family the operation ran
- * on, in the codes of fasp_hip_amg_kernel_info and from the same function, evaluated under the tune keys in force at the call: 4 k_csr_dict8,
- * 5 k_csr_rowpat, 6 k_csr_rowpat4, 9 k_csr_rowpat5, 7 k_csr_lstream, 8 k_csr_wstream2, 10 k_csr_xtile, 11 k_csr_sell, 0 k_csr_rows,
- * 2 k_csr_wstream.  A rectangular matrix (row != col) is accepted and uploaded the way a transfer operator is: it has no diagonal tables, so
+/* ... and of a matrix given on the host, uploaded the way a level's A is.  *kind_out (may be NULL) = the kernel family that serves y = M x on
+ * the whole operator -- whatever `op` is: a Jacobi sweep of an operator without diagonal positions, a smoother on a k_csr_rowpat5 operator and a
+ * row window may run on another one (fasp_hip_csr_plan tells) --, in the codes of fasp_hip_amg_kernel_info and from the same plan, evaluated under
+ * the tune keys in force at the call: 4 k_csr_dict8, 5 k_csr_rowpat, 6 k_csr_rowpat4, 9 k_csr_rowpat5, 7 k_csr_lstream, 8 k_csr_wstream2,
+ * 10 k_csr_xtile, 11 k_csr_sell, 0 k_csr_rows (and k_csr_estream), 2 k_csr_wstream.  A rectangular matrix (row != col) is accepted and uploaded the way a transfer operator is: it has no diagonal tables, so
  * ops 5 and 6 return ERROR_INPUT_PAR; x then holds col values, b / y / y2 row values. */
 int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out);
 /* test entry: ONE sequential block sweep of the host matrix A (square, storage_manner 0, 1 <= nb <= 7, a diagonal block in every row) on the

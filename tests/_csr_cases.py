@@ -135,6 +135,130 @@ def family(cd, nrow, ncol, nnz):
     return 9 if nnz <= 4.5 * nrow else 5
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# the kernel plan of a launch, restated
+# ------------------------------------------------------------------------------------------------------------------------------
+# the traits of fasp_hip_csr_plan (include/fasp_hip_dev.h), in its order: sizes, then 0 / 1 per pointer
+TRAITS = ("row", "col", "nnz", "kind", "lanes", "wrows", "wcap", "nxrows", "plane", "npat", "npent", "sell_nv", "sell_nslice", "sell_slots",
+          "ntcols", "es_W", "es_nc", "code", "pat", "rowbase", "dpos", "dup_diag", "ja16", "jbase", "lja16", "sell_code", "es_tab", "es_ja16")
+TRAIT_DEFAULTS = dict(dict.fromkeys(TRAITS, 0), lanes=8, wrows=64, wcap=512, nxrows=-1)     # a DevCSR as constructed
+# CsrKernel (csrc/device_csr.hip.h), in its order
+KERNELS = ("rows2", "rows4", "rows8", "rows16", "rows32", "rows64", "wstream_64_512", "wstream_64_1024", "wstream_32_512", "wstream_32_1024",
+           "rowpat_0_1", "rowpat_0_2", "rowpat_1_1", "rowpat_1_2", "rowpat_2_1", "rowpat_2_2", "dict8_8", "dict8_16", "dict8_24",
+           "estream4", "estream8", "estream16", "estream32", "rowpat4", "rowpat5", "lstream", "xtile", "sell", "wstream2")
+PLAN = ("kernel", "family", "tile_rows", "bpc", "xcd_map", "tpp", "nt", "ja16", "jbase", "fused_zr")     # the ints fasp_hip_csr_plan writes
+# the tune keys the plan reads, with their defaults (struct Tuning)
+TUNE_DEFAULTS = dict(gen2=2, ws2_bpc=3, xcd=16, nt=1, kind=-1, lanes=-1, wrows=-1, wcap=-1, compress=1, rpl=-1, lds_tab=1, xcd_pat=64, ja16=1,
+                     split_rows=0, xtile=1, rp5_max=45, rp_bpc=5, rp_xcd=-1, rp_strip=2, rp_stream=-1, estream=1, sell=1)
+OP_JACOBI, OP_L1DIAG, OP_MXV_DOT = 5, 6, 7
+SELL_BLOCK = 1024
+
+
+def expected_plan(t, op, windowed, want_partials, tune=None):
+    """The launch that launch_csr<op> of the commit BEFORE plan_csr existed (b70c478) made of an operator with the traits t, walked the
+    way that function walked: one `if` after the other, in its order, with its line of csrc/device_csr.hip.h beside each.  windowed: a
+    row window of all rows (win.hi >= 0).  -> dict of PLAN + bytes (the count its kernel_family gave the family, :1158-1173)."""
+    g = dict(TUNE_DEFAULTS, **(tune or {}))
+    M = dict(t)
+    row, nnz = M["row"], M["nnz"]
+    a = {}
+
+    def tiles(rpb):                                                                       # :1281 set_tiles
+        a["tile_rows"], a["ntiles"] = rpb, (row + rpb - 1) // rpb
+
+    def strips(rpb):                                                                      # :1294
+        if not g["rp_strip"] or M["plane"] < 8 * rpb or M["plane"] % (8 * rpb) != 0 or a["ntiles"] < 4 * (M["plane"] // rpb):
+            return
+        a["xcd_map"], a["tpp"] = -2, M["plane"] // rpb
+
+    def done(kernel, fam, bpc=0, fused=False):
+        base = 4.0 * row if M["rowbase"] else 0.0
+        if fam in (5, 6, 9): nbytes = 2.0 * row + base + 12.0 * M["npent"]                # :1161
+        elif fam == 4: nbytes = 1.0 * nnz + 4.0 * (row + 1.0) + base                      # :1160
+        elif fam == 10: nbytes = 10.0 * nnz + 4.0 * (row + 1.0) + 4.0 * M["ntcols"] + 4.0 * ((row + 63) // 64 + 1.0)      # :1169
+        elif fam == 11: nbytes = 4.0 * M["sell_slots"] + 1.0 * row + 4.0 * (2.0 * M["sell_nslice"] + 1.0) + 8.0 * M["sell_nv"]   # :1173
+        elif fam == 0 and a["ja16"]: nbytes = 10.0 * nnz + 4.0 * (row + 1.0) + (4.0 * row if a["jbase"] else 0.0)   # :1159
+        else: nbytes = 12.0 * nnz + 4.0 * (row + 1.0)                                     # :1158
+        return dict(kernel=KERNELS.index(kernel), family=fam, tile_rows=a["tile_rows"], bpc=bpc, xcd_map=a["xcd_map"], tpp=a.get("tpp", 0),
+                    nt=a["nt"], ja16=int(a["ja16"]), jbase=int(a["jbase"]), fused_zr=int(fused), bytes=nbytes)
+
+    windowed = windowed or g["split_rows"] > 0                                            # :1409 (win.hi < 0 && g_tune.split_rows <= 0)
+    if M["code"] and g["compress"]: M["kind"] = 4                                         # :1299
+    if M["pat"] and g["compress"]: M["kind"] = 5                                          # :1300
+    if g["kind"] >= 0 and not (g["kind"] == 4 and not M["code"]) and not (g["kind"] == 5 and not M["pat"]): M["kind"] = g["kind"]   # :1301
+    if g["lanes"] > 0: M["lanes"] = g["lanes"]                                            # :1302
+    if g["wrows"] > 0: M["wrows"] = g["wrows"]                                            # :1303
+    if g["wcap"] > 0: M["wcap"] = g["wcap"]                                               # :1304
+    w64 = M["wrows"] == 64 and M["wcap"] == 512
+    lstream_ok = bool(g["gen2"]) and M["kind"] == 2 and w64 and nnz <= 7.6 * row           # :1305
+    if op == OP_JACOBI and M["kind"] != 0 and M["kind"] < 4 and (M["dup_diag"] or not M["dpos"]) and not lstream_ok: M["kind"] = 0   # :1306
+    a["xcd_map"] = g["xcd"]                                                               # :1307
+    a["nt"] = g["nt"]                                                                     # :1308
+    if g["rp_stream"] > 0 or (g["rp_stream"] < 0 and row * 8 > 96 << 20): a["nt"] |= 4    # :1311
+    a["ja16"] = bool(g["ja16"] and M["ja16"])                                             # :1313
+    a["jbase"] = bool(g["ja16"] and M["jbase"])                                           # :1314
+    if M["jbase"] and M["kind"] != 0: a["ja16"] = a["jbase"] = False                      # :1315
+    if M["kind"] in (1, 3): M["kind"] = 0                                                 # :1316
+    tiles(BLOCK if M["kind"] >= 4 else 4 * M["wrows"] if M["kind"] == 2 else BLOCK // M["lanes"])     # :1317
+    jac_fused = op == OP_JACOBI and want_partials
+    diag_ok = op != OP_JACOBI or (M["dpos"] and not M["dup_diag"])
+    if M["kind"] == 5 and g["gen2"] and M["nxrows"] >= 0 and not M["rowbase"] and g["rpl"] <= 0:      # :1319
+        tiles(2 * BLOCK)                                                                  # :1323
+        a["xcd_map"] = g["rp_xcd"] if a["ntiles"] >= 8 * 64 else 16                       # :1324
+        if a["xcd_map"] == -1: strips(2 * BLOCK)                                          # :1326
+        return done("rowpat4", 6, 3 if a["xcd_map"] == -2 and g["rp_bpc"] == 5 else g["rp_bpc"], jac_fused)      # :1327, :1330
+    if (M["kind"] == 5 and g["gen2"] >= 2 and M["nxrows"] >= 0 and M["rowbase"] and g["rpl"] <= 0 and op not in (OP_JACOBI, OP_L1DIAG)
+            and nnz <= 0.1 * g["rp5_max"] * row):                                         # :1334
+        tiles(2 * BLOCK)                                                                  # :1339
+        a["xcd_map"] = -1 if a["ntiles"] >= 8 * 64 else 16                                # :1340
+        if g["rp_strip"] >= 2: strips(2 * BLOCK)                                          # :1341
+        return done("rowpat5", 9, 5)                                                      # :1342, :1214
+    if M["kind"] == 5:                                                                    # :1344
+        lds = M["npat"] <= 512 and M["npent"] <= 2048 and g["lds_tab"] != 0               # :1348
+        rpl = g["rpl"] if g["rpl"] > 0 else 1                                             # :1349
+        if g["xcd_pat"] != 0: a["xcd_map"] = g["xcd_pat"]                                 # :1351
+        tiles(BLOCK * rpl)                                                                # :1352
+        if g["xcd_pat"] == 64 and g["rp_strip"] >= 2: strips(BLOCK * rpl)                 # :1353
+        R = 1 if rpl == 1 else 2
+        if lds and M["npat"] <= 64 and M["npent"] <= 512 and g["lds_tab"] != 3: return done(f"rowpat_2_{R}", 5)     # :1355
+        if lds: return done(f"rowpat_1_{R}", 5)                                           # :1359
+        return done(f"rowpat_0_{R}", 5)                                                   # :1363
+    if M["kind"] == 4:                                                                    # :1366
+        avg = nnz / row if row > 0 else 1.0
+        return done("dict8_8" if avg <= 8.5 else "dict8_16" if avg <= 20.0 else "dict8_24", 4)     # :1369
+    if M["kind"] == 2 and g["gen2"] and w64 and nnz <= 7.6 * row:                         # :1373
+        return done("lstream", 7, 4, jac_fused)
+    if M["kind"] == 2 and g["gen2"] >= 2 and g["xtile"] and M["lja16"] and w64 and diag_ok:       # :1378
+        return done("xtile", 10, 3, jac_fused)
+    sell_active = M["sell_code"] and g["compress"] and g["sell"] and g["gen2"] >= 2 and not (g["xtile"] and M["lja16"])   # :1150
+    if M["kind"] == 2 and sell_active and w64 and diag_ok:                                # :1385
+        tiles(SELL_BLOCK)                                                                 # :1388
+        return done("sell", 11, 0, jac_fused)
+    if M["kind"] == 2 and g["gen2"] >= 2 and w64 and diag_ok:                             # :1392
+        return done("wstream2", 8, g["ws2_bpc"], jac_fused)
+    if M["kind"] == 2:                                                                    # :1397
+        return done("wstream_64_512" if w64 else "wstream_64_1024" if M["wrows"] == 64 else
+                    "wstream_32_512" if M["wrows"] == 32 and M["wcap"] == 512 else "wstream_32_1024", 2)
+    es_rule = g["estream"] >= 2 or (g["estream"] == 1 and nnz < 256.0 * row)              # :1408
+    if (M["es_tab"] and es_rule and a["ja16"] and not windowed and op != OP_MXV_DOT
+            and not (op == OP_JACOBI and (want_partials or M["dup_diag"]))):              # :1409
+        avg = nnz / row if row > 0 else 1.0
+        return done("estream32" if avg >= 512.0 else "estream16" if avg >= 256.0 else "estream8" if avg >= 128.0 else "estream4", 0)   # :1416
+    return done(f"rows{M['lanes']}" if M["lanes"] in (2, 4, 8, 16, 32) else "rows64", 0)  # :1441
+
+
+def fresh_traits(cd, nrow, ncol, nnz):
+    """The traits the plan reads of a freshly uploaded matrix with the coding cd (upload_csr; the 16-bit copies and the k_csr_estream,
+    k_csr_xtile and k_csr_sell forms belong to uncoded operators)."""
+    t = dict(TRAIT_DEFAULTS, row=nrow, col=ncol, nnz=nnz, kind=2 if nnz <= 48.0 * nrow else 0, rowbase=int(nrow != ncol), dpos=int(nrow == ncol))
+    if cd["kind"] == 5:
+        nx, _ = off_pattern(cd["pat"], nrow, nrow == ncol)
+        t.update(pat=1, npat=cd["npat"], npent=cd["npent"], nxrows=nx if nx * 4 <= nrow else -1)
+    elif cd["kind"] == 4:
+        t.update(code=1)
+    return t
+
+
 def grid_plane(poff, nrow):
     """grid_plane_of: the row distance the XCD strips of a square pattern-coded operator are cut along (0: none)."""
     unit = 8 * PAIR_TILE
