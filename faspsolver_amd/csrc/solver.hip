@@ -2412,6 +2412,33 @@ int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* 
     return st;
 }
 
+// Test entry: the traits plan_csr reads (fasp_hip_csr_plan's layout, fasp_hip_dev.h) of the device copy fasp_hip_matrix_op makes of A -- the same
+// upload_csr, and upload_diag for a square matrix -- so that a test can ask fasp_hip_csr_plan for the kernel of every operation on that very copy.
+int fasp_hip_matrix_traits(const dCSRmat* A, int* traits)
+{
+    FASP_ENTRY();
+    if (!A || !traits || ctx_init() < 0) return ERROR_INPUT_PAR;
+    HostCSR M;
+    M.row = A->row; M.col = A->col; M.nnz = A->nnz;
+    M.ia.view(A->IA, (size_t)A->row + 1); M.ja.view(A->JA, (size_t)std::max(A->nnz, 1)); M.val.view(A->val, (size_t)std::max(A->nnz, 1));
+    DevLevel D;
+    int st;
+    {
+        HostThreads team;
+        st = upload_csr(M, D.A);
+        if (st >= 0 && M.row == M.col) st = upload_diag(M, D);
+    }
+    if (st >= 0) {
+        const DevCSR& d = D.A;
+        const int out[28] = {d.row, d.col, d.nnz, d.kind, d.lanes, d.wrows, d.wcap, d.nxrows, d.plane, d.npat, d.npent, d.sell_nv, d.sell_nslice,
+                             (int)d.sell_slots, (int)d.ntcols, d.es_W, d.es_nc, d.code != nullptr, d.pat != nullptr, d.rowbase != nullptr, d.dpos != nullptr,
+                             d.dup_diag, d.ja16 != nullptr, d.jbase != nullptr, d.lja16 != nullptr, d.sell_code != nullptr, d.es_tab != nullptr, d.es_ja16 != nullptr};
+        std::copy(out, out + 28, traits);
+    }
+    free_level(D);
+    return st < 0 ? st : FASP_SUCCESS;
+}
+
 // Development / test entry: one operator through the resident upload path (lossless coding, kernel selection as for a
 // hierarchy level) timed with HIP events on the launch stream.  op: 0 y = A x, 1 y -= A x, 2 Jacobi sweep, 5 y = A x
 // fused with (y, x).  Returns milliseconds per launch (< 0: error); *kind_out = the family (codes of fasp_hip_amg_kernel_info) of

@@ -186,6 +186,9 @@ int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const doub
  * 10 k_csr_xtile, 11 k_csr_sell, 0 k_csr_rows (and k_csr_estream), 2 k_csr_wstream.  A rectangular matrix (row != col) is accepted and uploaded the way a transfer operator is: it has no diagonal tables, so
  * ops 5 and 6 return ERROR_INPUT_PAR; x then holds col values, b / y / y2 row values. */
 int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red, int* kind_out);
+/* test entry: the 28 traits of fasp_hip_csr_plan's layout read from the device copy fasp_hip_matrix_op makes of A (the same upload; the diagonal
+ * tables for a square matrix), which is freed again: with them fasp_hip_csr_plan names the kernel of every operation on that copy. */
+int  fasp_hip_matrix_traits(const dCSRmat* A, int* traits);
 /* test entry: ONE sequential block sweep of the host matrix A (square, storage_manner 0, 1 <= nb <= 7, a diagonal block in every row) on the
  * device, through the level schedule and the per-level launches the block AMG cycle smooths with: block Gauss-Seidel (sor = 0; w unused) or
  * block SOR with weight w, rows ascending (descend = 0) or descending, u updated in place.  diaginv: the ROW inverse diagonal blocks
