@@ -57,7 +57,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_ilu_dbsr_setup", "fasp_precond_dbsr_ilu", "fasp_solver_dbsr_krylov_ilu", "fasp_smoother_dbsr_ilu",
     "fasp_fwrapper_dbsr_krylov_ilu_",
     "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
-    "fasp_hip_bsr_sweep",
+    "fasp_hip_bsr_sweep", "fasp_hip_csr_sweep",
     "fasp_blas_dcsr_rap", "fasp_hip_dcsr_rap", "fasp_hip_rap_info", "fasp_hip_rap_device_count", "fasp_hip_rap_time",
 ]
 
@@ -115,6 +115,8 @@ def lib():
     L.fasp_dbsr_getdiaginv.restype = T.dvector
     L.fasp_smoother_dbsr_jacobi1.argtypes = [P(T.dBSRmat), P(T.dvector), P(T.dvector), T.c_double_p]
     L.fasp_hip_bsr_sweep.argtypes = [P(T.dBSRmat), T.c_double_p, T.c_double_p, T.c_double_p, C.c_int, C.c_int, C.c_double,
+                                     P(C.c_int)]
+    L.fasp_hip_csr_sweep.argtypes = [P(T.dCSRmat), P(C.c_int), C.c_int, C.c_int, C.c_double, C.c_int, T.c_double_p, T.c_double_p,
                                      P(C.c_int)]
     L.fasp_hip_time_bsr_mxv.argtypes = [P(T.dBSRmat), C.c_int]
     L.fasp_hip_time_bsr_mxv.restype = C.c_double

@@ -38,6 +38,11 @@ struct DevLevel {
         bool chain = false; int nb = 0, npad = 0, n1b = 0, rx = 0, rg = 0; long long t1_steps = 0, t2_steps = 0, nband = 0, nt1 = 0, nt2 = 0;
         double* d_band = nullptr; double* d_drd = nullptr; void* d_blk = nullptr; double* d_t1v = nullptr; double* d_t2v = nullptr;
         unsigned short* d_t1c = nullptr; unsigned short* d_t2c = nullptr; double* d_G2 = nullptr; int* d_t1need = nullptr; int* d_t2need = nullptr;
+        // what the last launch of this schedule ran (set at the launch sites of seq_sweep_launch, smoothers.hip.h; read by fasp_hip_csr_sweep):
+        // path 0 nothing, 1 k_split_direct, 2 rest + k_split_scatter(final), 3 rest + k_tri_flow, 4 rest + k_tri_level + scatter, 5 rest + k_tri_chain,
+        // 6 rest + k_tri_chain_ref, 7 k_seq_level per whole-row dependency level, 8 k_seq_level per colour; lanes / rounds of the instantiation of
+        // pass (2) (0: it has none), lanes of the rest pass, launches of pass (2)
+        int run_path = 0, run_L = 0, run_rounds = 0, run_LR = 0, run_launches = 0;
         std::vector<void*> owned;   // device arrays of the split form (d_order and d_ptr among them)
         void release()
         {

@@ -277,6 +277,75 @@ void smoother_standalone(const char* fn, dvector* u, int i_1, int i_n, int s, dC
     if (st < 0) { std::fprintf(stderr, "### ERROR: %s: sweep failed (%d)\n", fn, st); std::exit(st); }
 }
 }  // namespace
+// test entry: ONE sequential sweep over the rows seq[0..ns) of a host matrix, through the schedule builders and the launch half of the cycle's
+// sweeps (smoothers.hip.h: seq_schedule_build, seq_sweep_launch) under the tune keys in force
+int fasp_hip_csr_sweep(const dCSRmat* A, const int* seq, int ns, int form, double w, int zero_start, const double* b, double* u, int* info)
+{
+    FASP_ENTRY();
+    if (!A || !b || !u || ns < 0 || (ns > 0 && !seq) || A->row != A->col || A->row < 0 || A->nnz < 0 || !A->IA || (A->nnz > 0 && (!A->JA || !A->val)))
+        return ERROR_INPUT_PAR;
+    if (form < 0 || form > 2 || ns > A->row) return ERROR_INPUT_PAR;
+    const int n = A->row;
+    {
+        std::vector<char> seen((size_t)std::max(n, 1), 0);
+        for (int q = 0; q < ns; ++q) {
+            if (seq[q] < 0 || seq[q] >= n || seen[(size_t)seq[q]]) return ERROR_INPUT_PAR;
+            seen[(size_t)seq[q]] = 1;
+        }
+    }
+    if (info) std::fill(info, info + 12, 0);
+    if (n == 0) return FASP_SUCCESS;
+    if (ctx_init() < 0) return ERROR_MISC;
+    AMG_param p;
+    fasp_param_amg_init(&p);
+    p.max_levels = 1; p.print_level = 0;   // one level: the operator itself, resident (as smoother_standalone)
+    p.smoother = SMOOTHER_JACOBI;          // (no schedule jobs of the hierarchy's own: the schedule below is this sweep's)
+    fasp_hip_amg* h = nullptr;
+    if (fasp_hip_amg_create(&h, A, &p) < 0) return ERROR_MISC;
+    DevLevel& D = h->L[0];
+    DevLevel::Sched& S = D.sched[0];   // (released with the level)
+    D.b = h->b;
+    int st = FASP_SUCCESS;
+    if (hipMemcpyAsync(D.b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream) != hipSuccess) st = ERROR_MISC;
+    if (zero_start) D.x_zero = true;   // the level's vector is flagged all-zero: pass (1) may skip it (seq_zero_skip)
+    else {
+        if (hipMemcpyAsync(D.x, u, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream) != hipSuccess) st = ERROR_MISC;
+        D.x_zero = false;
+    }
+    if (st >= 0) st = seq_schedule_build(h->H.L[0].A, std::vector<int>(seq, seq + ns), S, g_tune.gs_multicolor != 0);
+    if (st >= 0) st = seq_sweep_launch(D, S, form, w);
+    if (hipStreamSynchronize(g_ctx.stream) != hipSuccess && st >= 0) st = ERROR_MISC;
+    if (seq_err_check() < 0 && st >= 0) st = ERROR_MISC;   // a poll of this sweep (or of an earlier one) that ran out
+    if (st >= 0) {
+        std::vector<double> x((size_t)n);
+        if (hipMemcpy(x.data(), D.x, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) st = ERROR_MISC;
+        else if (!zero_start) std::copy(x.begin(), x.end(), u);   // the device's WHOLE vector: a store outside the sweep shows in the caller's u
+        else {
+            // the caller's u was never on the device: the rows outside the sweep must still hold the +0.0 of the flagged vector
+            std::vector<char> swept((size_t)n, 0);
+            for (int q = 0; q < ns; ++q) swept[(size_t)seq[q]] = 1;
+            for (int i = 0; i < n && st >= 0; ++i) {
+                unsigned long long bits;
+                std::memcpy(&bits, &x[(size_t)i], 8);
+                if (!swept[(size_t)i] && bits != 0ull) {
+                    std::fprintf(stderr, "### ERROR: fasp_hip_csr_sweep: row %d lies outside the sweep and was written (%.17g)\n", i, x[(size_t)i]);
+                    st = ERROR_MISC;
+                }
+            }
+            for (int q = 0; q < ns && st >= 0; ++q) u[seq[q]] = x[(size_t)seq[q]];
+        }
+    }
+    if (st >= 0 && info) {
+        info[0] = S.run_path; info[1] = S.run_L; info[2] = S.run_rounds; info[3] = S.run_LR;
+        const bool split = S.run_path == 3 || S.run_path == 4, chain = S.run_path == 5 || S.run_path == 6;
+        info[4] = split ? S.kt : 0; info[5] = split ? S.nvirt : 0; info[6] = split ? S.nstrips : 0; info[7] = split ? S.nchunk : 0;
+        info[8] = S.run_launches;
+        info[9] = chain ? S.n1b : 0; info[10] = chain ? (int)S.t1_steps : 0; info[11] = chain ? (int)S.t2_steps : 0;
+    }
+    fasp_hip_amg_destroy(h);
+    return st;
+}
+
 // ItrSmootherCSR.c:251: s = +1 ascending, -1 descending, u_i = t * (1 / a_ii)
 void fasp_smoother_dcsr_gs(dvector* u, const int i_1, const int i_n, const int s, dCSRmat* A, dvector* b, int L)
 {

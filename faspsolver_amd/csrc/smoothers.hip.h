@@ -343,8 +343,23 @@ static void sched_jobs_join(fasp_hip_amg* h)   // (hierarchy teardown)
     h->sched_jobs.clear();
 }
 
-// one sequential sweep of schedule `kind` with update formula `form` (see tri_update) over the rows THIS rank holds of the level
-static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, double w)
+// The schedule of the rows `seq` (in sweep order) of the host matrix A under the tune keys in force: the split form (or the chain form inside
+// it), whole-row dependency levels where a row reads more earlier rows than a strip holds, colour classes in the multicolour mode.
+// st: what a schedule job has answered for the split form already (1000: nobody has built anything yet).
+static int seq_schedule_build(const HostCSR& A, const std::vector<int>& seq, DevLevel::Sched& S, bool multicolor, int st = 1000)
+{
+    if (st == 1000) st = multicolor ? build_schedule(A, seq, S, true) : build_split(A, seq, S);
+    if (st < 0) return st;
+    S.rowlevels = false;
+    if (st == 1) {   // a row of this sweep reads more earlier rows than a strip's LDS holds: whole rows, one launch per dependency level
+        if ((st = build_schedule(A, seq, S, false)) < 0) return st;
+        S.rowlevels = true;
+    }
+    return FASP_SUCCESS;
+}
+
+// first half of a sequential sweep of the cycle: the schedule of sweep `kind` over the rows THIS rank holds of the level, built on first use
+static int seq_sweep_schedule(fasp_hip_amg* h, int level, int kind)
 {
     DevLevel& D = h->L[level];
     DevLevel::Sched& S = D.sched[kind];
@@ -382,13 +397,7 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
                 }
         }
         if (st == 1000 || st == 1) sweep_sequence(h->H.L[level], kind, seq, D.replicated ? 0 : D.row0, D.replicated ? -1 : D.nloc);
-        if (st == 1000) st = multicolor ? build_schedule(A, seq, S, true) : build_split(A, seq, S);
-        if (st < 0) return st;
-        S.rowlevels = false;
-        if (st == 1) {   // a row of this sweep reads more earlier rows than a strip's LDS holds: whole rows, one launch per dependency level
-            if ((st = build_schedule(A, seq, S, false)) < 0) return st;
-            S.rowlevels = true;
-        }
+        if ((st = seq_schedule_build(A, seq, S, multicolor, st)) < 0) return st;
         if (std::getenv("FASP_HIP_SETUP_TIMING")) {
             if (S.chain) std::printf("  [sweep schedule] level %d, sweep kind %d: CHAIN form, %d rows in %d dependency classes, %d blocks of 64, band %lld entries, tier 1 (%d blocks, ring of %d) %lld entries in %lld steps, "
                                      "tier 2 %lld entries in %lld steps, rest pass %d lanes per row, built in %.3f s\n", level, kind, S.nrows, S.nclasses, S.nb, S.nband, S.n1b, S.rx, S.nt1, S.t1_steps, S.nt2, S.t2_steps, S.LR, wall_seconds() - t0);
@@ -399,6 +408,15 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
                              "", wall_seconds() - t0);
         }
     }
+    return FASP_SUCCESS;
+}
+
+// second half: the launches of one sweep of the schedule S with update formula `form` (see tri_update) on the level's vectors.  Shared by the
+// cycle (seq_sweep_local) and the test entry fasp_hip_csr_sweep (precond_api.hip.h); every launch site says in S.run_* what it ran.
+static int seq_sweep_launch(DevLevel& D, DevLevel::Sched& S, int form, double w)
+{
+    const bool multicolor = S.multicolor;
+    S.run_path = 0; S.run_L = 0; S.run_rounds = 0; S.run_LR = 0; S.run_launches = 0;
     // the level's vector is all zeros when this sweep starts (the first sweep of a pre-smoothing step; one rank -- in a sweep by turns the
     // halo has been exchanged by then): pass (1) has nothing to read but b
     const int zero_old = (D.x_zero && g_tune.seq_zero_skip && (D.replicated || comm_size() <= 1)) ? 1 : 0;
@@ -412,9 +430,9 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             const int lo = S.ptr[l], hi = S.ptr[l + 1];
             const int rpb = BLOCK / L;
             const int grid = std::max(1, std::min(MAXGRID, (hi - lo + rpb - 1) / rpb));
-#define SEQ_LAUNCH(LL) hipLaunchKernelGGL((k_seq_level<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, \
+#define SEQ_LAUNCH(LL) do { hipLaunchKernelGGL((k_seq_level<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, \
             (const int*)S.d_order, lo, hi, (const int*)D.A.ia, (const int*)D.A.ja, (const double*)D.A.val,    \
-            (const double*)D.b, (const double*)D.diag, D.x, form, w)
+            (const double*)D.b, (const double*)D.diag, D.x, form, w); S.run_L = LL; } while (0)
             switch (L) {
                 case 2: SEQ_LAUNCH(2); break;
                 case 4: SEQ_LAUNCH(4); break;
@@ -425,6 +443,7 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             }
 #undef SEQ_LAUNCH
         }
+        if (nlev > 0) { S.run_path = multicolor ? 8 : 7; S.run_launches = nlev; }
         return FASP_SUCCESS;
     }
     const int ns = S.chain ? S.nrows : S.ns;   // (chain form: S.ns = positions padded to blocks of 64; the rest pass runs over the rows)
@@ -437,8 +456,8 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
     if (S.nolower && S.independent && !S.chain) {   // the rows of the sweep do not couple: one pass, in place
         const int rpb = BLOCK / S.LR;
         const int grid = std::max(1, std::min(MAXGRID, (ns + rpb - 1) / rpb));
-#define DIRECT_LAUNCH(LL) hipLaunchKernelGGL((k_split_direct<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, ns, (const int*)S.d_tr, \
-        (const int*)S.d_ria, (const int*)S.d_rja, (const double*)S.d_rval, (const double*)S.d_dr, (const double*)D.b, D.x, form, w, zero_old)
+#define DIRECT_LAUNCH(LL) do { hipLaunchKernelGGL((k_split_direct<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, ns, (const int*)S.d_tr, \
+        (const int*)S.d_ria, (const int*)S.d_rja, (const double*)S.d_rval, (const double*)S.d_dr, (const double*)D.b, D.x, form, w, zero_old); S.run_LR = LL; } while (0)
         switch (S.LR) {
             case 1: DIRECT_LAUNCH(1); break;
             case 2: DIRECT_LAUNCH(2); break;
@@ -449,15 +468,16 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             default: DIRECT_LAUNCH(64); break;
         }
 #undef DIRECT_LAUNCH
+        S.run_path = 1;
         return FASP_SUCCESS;
     }
     // pass (1): everything that reads old values, all rows at once
     {
         const int rpb = BLOCK / S.LR;
         const int grid = std::max(1, std::min(MAXGRID, (ns + rpb - 1) / rpb));
-#define REST_LAUNCH(LL) hipLaunchKernelGGL((k_split_rest<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, ns, (const int*)S.d_tr, \
+#define REST_LAUNCH(LL) do { hipLaunchKernelGGL((k_split_rest<LL>), dim3(grid), dim3(BLOCK), 0, g_ctx.stream, ns, (const int*)S.d_tr, \
         (const int*)S.d_ria, (const int*)S.d_rja, (const double*)S.d_rval, (const double*)D.b, (const double*)D.x, S.d_rec, S.d_W, S.d_prog, \
-        S.chain ? S.d_G2 : (double*)nullptr, S.chain ? S.npad : 0, zero_old)
+        S.chain ? S.d_G2 : (double*)nullptr, S.chain ? S.npad : 0, zero_old); S.run_LR = LL; } while (0)
         switch (S.LR) {
             case 1: REST_LAUNCH(1); break;
             case 2: REST_LAUNCH(2); break;
@@ -492,12 +512,14 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             default: CHAIN_LAUNCH(2); break;
         }
 #undef CHAIN_LAUNCH
+        S.run_path = plain ? 6 : 5; S.run_L = 64; S.run_launches = 1;
         if (!plain) seq_err_watch(S.d_prog + 1);
         return FASP_SUCCESS;
     }
     const int sgrid = std::max(1, std::min(MAXGRID, (ns + BLOCK - 1) / BLOCK));
     if (S.nolower) {   // no row of the sweep reads another one's new value (the C rows / F rows of the 7-point level 0)
         hipLaunchKernelGGL(k_split_scatter, dim3(sgrid), dim3(BLOCK), 0, g_ctx.stream, ns, fa, 1);
+        S.run_path = 2; S.run_launches = 1;
         return FASP_SUCCESS;
     }
     // pass (2), the dataflow form: one launch, workgroups draw strips from the ticket counter (seq_split.hip.h)
@@ -517,6 +539,7 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             const int nt = FlowGeom<PP>::NT, per_cu = std::max(1, std::min(2048 / nt, by_lds));                             \
             const int grid = std::max(1, std::min(std::min(S.nstrips, per_cu * g_ctx.num_cu), g_tune.seq_grid > 0 ? g_tune.seq_grid : g_tune.seq_grid < 0 || S.par >= S.nstrips ? 1 << 30 : 2 * S.par + 2)); \
             hipLaunchKernelGGL((k_tri_flow<LL, PP>), dim3(grid), dim3(nt), dyn, g_ctx.stream, fa);                      \
+            S.run_L = LL; S.run_rounds = PP;                                                                                \
         }
 #define FLOW_LAUNCH(LL)                                                                                                     \
         if (S.pfmax > 4) FLOW_ONE(LL, TRI_PFMAX)                                                                            \
@@ -532,6 +555,7 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
         }
 #undef FLOW_LAUNCH
 #undef FLOW_ONE
+        S.run_path = 3; S.run_launches = 1;
         seq_err_watch(S.d_prog + 1);
         return FASP_SUCCESS;
     }
@@ -540,8 +564,9 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
     for (int l = 0; l < nlev; ++l) {
         const int c0 = S.cptr[l], grid = S.cptr[l + 1] - c0;
         if (grid <= 0) continue;
-#define TRIL_LAUNCH(LL) if (S.pfmax > 4) hipLaunchKernelGGL((k_tri_level<LL, TRI_PFMAX>), dim3(grid), dim3(64), 0, g_ctx.stream, fa, (const int*)S.d_lchunks, c0); \
-                        else hipLaunchKernelGGL((k_tri_level<LL, 4>), dim3(grid), dim3(64), 0, g_ctx.stream, fa, (const int*)S.d_lchunks, c0)
+#define TRIL_ONE(LL, PP) do { hipLaunchKernelGGL((k_tri_level<LL, PP>), dim3(grid), dim3(64), 0, g_ctx.stream, fa, (const int*)S.d_lchunks, c0); \
+                              S.run_L = LL; S.run_rounds = PP; } while (0)
+#define TRIL_LAUNCH(LL) if (S.pfmax > 4) TRIL_ONE(LL, TRI_PFMAX); else TRIL_ONE(LL, 4)
         switch (L) {
             case 1: TRIL_LAUNCH(1); break;
             case 2: TRIL_LAUNCH(2); break;
@@ -552,9 +577,20 @@ static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, doubl
             default: TRIL_LAUNCH(64); break;
         }
 #undef TRIL_LAUNCH
+#undef TRIL_ONE
+        ++S.run_launches;
     }
     hipLaunchKernelGGL(k_split_scatter, dim3(sgrid), dim3(BLOCK), 0, g_ctx.stream, ns, fa, 0);
+    S.run_path = 4; ++S.run_launches;
     return FASP_SUCCESS;
+}
+
+// one sequential sweep of schedule `kind` with update formula `form` (see tri_update) over the rows THIS rank holds of the level
+static int seq_sweep_local(fasp_hip_amg* h, int level, int kind, int form, double w)
+{
+    const int st = seq_sweep_schedule(h, level, kind);
+    if (st < 0) return st;
+    return seq_sweep_launch(h->L[level], h->L[level].sched[kind], form, w);
 }
 
 // A sequential sweep of a ROW-PARTITIONED level (round 4; fasp_hip_tune("seq_partition", 1) or FASP_HIP_SEQ_PARTITION=1 before the

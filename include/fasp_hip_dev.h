@@ -195,6 +195,23 @@ int  fasp_hip_matrix_traits(const dCSRmat* A, int* traits);
  * (fasp_dbsr_getdiaginv).  *nlevels = dependency levels of the schedule (launches of the sweep).  Bad arguments (a NULL pointer, nb outside
  * 1..7, storage_manner != 0, ROW != COL) return ERROR_INPUT_PAR and touch nothing; no usable device: ERROR_MISC. */
 int  fasp_hip_bsr_sweep(const dBSRmat* A, const double* b, double* u, const double* diaginv, int descend, int sor, double w, int* nlevels);
+/* test entry: ONE sequential sweep (Gauss-Seidel / SOR family) over the rows seq[0..ns) of the host matrix A (square), in that order, on the
+ * device: A is uploaded as a one-level hierarchy, the schedule of `seq` is built by the builders of the cycle's sweeps under the tune keys in
+ * force (split form, chain form inside it, whole-row dependency levels where a row reads more earlier rows than a strip holds, colour classes
+ * under gs_multicolor) and launched by the launch half of the cycle's sweep.  seq: any subset of the rows without repeats.  form: 0 u_i = t *
+ * (1 / a_ii), 1 u_i = t / a_ii, 2 u_i = w (t / a_ii) + (1 - w) u_i, with t = b_i - sum_{j != i} a_ij u_j; rows with |a_ii| <= 1e-20 (the last
+ * diagonal stored counts) are left alone.  u is uploaded in full and comes back in full -- the device's whole vector, so that a store outside
+ * the sweep shows as a changed row of u.  zero_start = 1: the level's vector is flagged all-zero and the input u is ignored and never uploaded;
+ * only the swept rows are written back (a row the sweep leaves alone comes back as the +0.0 it holds there), and the entry itself checks that
+ * every row outside the sweep still holds +0.0 on the device: ERROR_MISC (and a line on stderr naming the row) when one does not.
+ * info (12 ints, may be NULL), set at the launch sites: {path -- 0 nothing to do, 1 k_split_direct, 2 k_split_rest + k_split_scatter(final), 3
+ * k_split_rest + k_tri_flow, 4 k_split_rest + k_tri_level per dependency class + k_split_scatter, 5 k_split_rest + k_tri_chain, 6 k_split_rest
+ * + k_tri_chain_ref, 7 k_seq_level per whole-row dependency level, 8 k_seq_level per colour --, lanes per row L of the instantiation of pass
+ * (2) (paths 3 .. 8; the chain forms: 64), its rounds (4 or 8; paths 3 and 4), lanes per row LR of k_split_rest / k_split_direct (paths 1 ..
+ * 6), spine rounds, virtual rows, strips, chunks (paths 3 and 4), launches of pass (2) (path 1: 0), chain form: blocks of tier 1, steps of
+ * tier 1, steps of tier 2}.  A NULL pointer, row != col, form outside 0 .. 2, a seq entry out of range or repeated: ERROR_INPUT_PAR, nothing
+ * is touched; no usable device: ERROR_MISC; a poll of the dataflow / chain form that ran out: ERROR_MISC (and the report of seq_err_check). */
+int  fasp_hip_csr_sweep(const dCSRmat* A, const int* seq, int ns, int form, double w, int zero_start, const double* b, double* u, int* info);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 

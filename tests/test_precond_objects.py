@@ -200,26 +200,12 @@ def test_standalone_sweeps_on_a_ragged_matrix(gpu, which):
     an unsymmetric pattern (anti-dependencies), rows far longer than the slot storage holds (tails), empty rows, rows
     without a diagonal and with a zero diagonal (left alone, ItrSmootherCSR.c: |d| <= SMALLREAL), a diagonal stored
     twice (the reference's loop keeps the LAST one and subtracts nothing for either)."""
-    import scipy.sparse as sp
+    from _sweep_cases import ragged700
     L = fa.lib()
-    rng = np.random.default_rng(5)
+    ia, ja, a = ragged700()                       # (the generator lives with the other sweep cases: tests/_sweep_cases.py)
     n = 700
-    M = sp.random(n, n, density=0.03, random_state=7, format="lil")
-    for i in (3, 250, 699):                       # very long rows: more lower entries than 8 x 64 slots
-        M[i, :] = rng.standard_normal(n)
-    for i in range(n): M[i, i] = 30.0 + rng.random()
-    for i in (10, 11, 400): M[i, :] = 0.0         # empty rows
-    M[20, 20] = 0.0                               # stored zero diagonal
-    M = M.tocsr(); M.sort_indices()
-    M[21, 21] = 0.0; M.eliminate_zeros()          # no diagonal at all in row 21 (row 20 lost its zero too: put it back below)
-    ia = M.indptr.astype(np.int32).tolist(); ja = M.indices.astype(np.int32).tolist(); a = M.data.tolist()
-    def insert(row, col, v):                      # append an entry to a row (unsorted storage is allowed)
-        k = ia[row + 1]
-        ja.insert(k, col); a.insert(k, v)
-        for r in range(row + 1, n + 1): ia[r] += 1
-    insert(20, 20, 0.0)                           # zero diagonal, stored
-    insert(100, 100, 55.0)                        # diagonal stored twice: the last one counts
-    ia = np.array(ia, dtype=np.int32); ja = np.array(ja, dtype=np.int32); a = np.array(a)
+    rng = np.random.default_rng(5)
+    rng.standard_normal(3 * n); rng.random(n)     # (what the generator draws from the same stream: f and u0 stay what they were)
     f = rng.standard_normal(n); u0 = rng.standard_normal(n)
     A, keep = T.as_csr(ia, ja, a)
     u = u0.copy(); uv, u = T.as_vec(u); bv, _f = T.as_vec(f)
