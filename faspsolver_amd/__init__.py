@@ -59,6 +59,10 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
     "fasp_hip_bsr_sweep", "fasp_hip_csr_sweep",
     "fasp_blas_dcsr_rap", "fasp_hip_dcsr_rap", "fasp_hip_rap_info", "fasp_hip_rap_device_count", "fasp_hip_rap_time",
+    "fasp_dstr_create", "fasp_dstr_alloc", "fasp_dstr_free", "fasp_dstr_cp", "fasp_format_dstr_dcsr", "fasp_dstr_read",
+    "fasp_blas_dstr_aAxpy", "fasp_blas_dstr_mxv", "fasp_precond_dstr_diag", "fasp_solver_dstr_pcg", "fasp_solver_dstr_pbcgs",
+    "fasp_solver_dstr_pminres", "fasp_solver_dstr_pgmres", "fasp_solver_dstr_pvgmres", "fasp_solver_dstr_itsolver",
+    "fasp_solver_dstr_krylov", "fasp_solver_dstr_krylov_diag", "fasp_hip_mxv_str", "fasp_hip_str_form", "fasp_hip_time_str_mxv",
 ]
 
 
@@ -266,6 +270,39 @@ def lib():
     L.fasp_hip_rap_time.restype = C.c_double
     L.fasp_dcsr_free.argtypes = [P(T.dCSRmat)]
     L.fasp_dcsr_free.restype = None
+    # structured (STR) matrices
+    L.fasp_dstr_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, T.c_int_p]
+    L.fasp_dstr_create.restype = T.dSTRmat
+    L.fasp_dstr_alloc.argtypes = [C.c_int] * 7 + [T.c_int_p, P(T.dSTRmat)]
+    L.fasp_dstr_alloc.restype = None
+    L.fasp_dstr_free.argtypes = [P(T.dSTRmat)]
+    L.fasp_dstr_free.restype = None
+    L.fasp_dstr_cp.argtypes = [P(T.dSTRmat), P(T.dSTRmat)]
+    L.fasp_dstr_cp.restype = None
+    L.fasp_format_dstr_dcsr.argtypes = [P(T.dSTRmat), P(T.dCSRmat)]
+    L.fasp_format_dstr_dcsr.restype = C.c_short
+    L.fasp_dstr_read.argtypes = [C.c_char_p, P(T.dSTRmat)]
+    L.fasp_hip_str_form.argtypes = [P(T.dSTRmat)]
+    L.fasp_hip_time_str_mxv.argtypes = [P(T.dSTRmat), C.c_int]
+    L.fasp_hip_time_str_mxv.restype = C.c_double
+    L.fasp_blas_dstr_aAxpy.argtypes = [C.c_double, P(T.dSTRmat), T.c_double_p, T.c_double_p]
+    L.fasp_blas_dstr_aAxpy.restype = None
+    L.fasp_blas_dstr_mxv.argtypes = [P(T.dSTRmat), T.c_double_p, T.c_double_p]
+    L.fasp_blas_dstr_mxv.restype = None
+    L.fasp_precond_dstr_diag.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_dstr_diag.restype = None
+    L.fasp_solver_dstr_pcg.argtypes = [P(T.dSTRmat), P(T.dvector), P(T.dvector), P(T.precond), C.c_double,
+                                       C.c_double, C.c_int, C.c_short, C.c_short]
+    L.fasp_solver_dstr_pbcgs.argtypes = L.fasp_solver_dstr_pcg.argtypes
+    L.fasp_solver_dstr_pminres.argtypes = L.fasp_solver_dstr_pcg.argtypes
+    L.fasp_solver_dstr_pgmres.argtypes = [P(T.dSTRmat), P(T.dvector), P(T.dvector), P(T.precond), C.c_double,
+                                          C.c_double, C.c_int, C.c_short, C.c_short, C.c_short]
+    L.fasp_solver_dstr_pvgmres.argtypes = L.fasp_solver_dstr_pgmres.argtypes
+    L.fasp_solver_dstr_itsolver.argtypes = [P(T.dSTRmat), P(T.dvector), P(T.dvector), P(T.precond), P(T.ITS_param)]
+    L.fasp_solver_dstr_krylov.argtypes = [P(T.dSTRmat), P(T.dvector), P(T.dvector), P(T.ITS_param)]
+    L.fasp_solver_dstr_krylov_diag.argtypes = L.fasp_solver_dstr_krylov.argtypes
+    L.fasp_hip_mxv_str.argtypes = [C.c_void_p, T.c_double_p, T.c_double_p]
+    L.fasp_hip_mxv_str.restype = None
     return L
 
 

@@ -45,6 +45,7 @@ SMOOTHER_JACOBIF, SMOOTHER_GSF = 11, 12
 COARSE_RS, COARSE_RSP, COARSE_CR, COARSE_AC, COARSE_MIS = 1, 2, 3, 4, 5
 INTERP_DIR, INTERP_STD, INTERP_ENG, INTERP_RDC, INTERP_EXT = 1, 2, 3, 4, 6
 NO_ORDER, CF_ORDER = 0, 1
+MAT_FREE, MAT_CSR, MAT_BSR, MAT_STR = 0, 1, 2, 3
 
 
 class dCSRmat(C.Structure):
@@ -57,8 +58,20 @@ class dBSRmat(C.Structure):
                 ("storage_manner", C.c_int), ("val", c_double_p), ("IA", c_int_p), ("JA", c_int_p)]
 
 
+class dSTRmat(C.Structure):
+    """fasp.h:316: banded block matrix on a structured grid (sizeof == 64)."""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("nxy", C.c_int), ("nc", C.c_int),
+                ("ngrid", C.c_int), ("diag", c_double_p), ("nband", C.c_int), ("offsets", c_int_p),
+                ("offdiag", C.POINTER(c_double_p))]
+
+
 class dvector(C.Structure):
     _fields_ = [("row", C.c_int), ("val", c_double_p)]
+
+
+class precond_diag_str(C.Structure):
+    """fasp.h:1074: inverse diagonal blocks of a dSTRmat."""
+    _fields_ = [("nc", C.c_int), ("diag", dvector)]
 
 
 class ivector(C.Structure):
@@ -126,6 +139,22 @@ def as_bsr(ia, ja, val, nb, ncol=None):
     A = dBSRmat(n, n if ncol is None else ncol, int(ia[-1]), nb, 0, val.ctypes.data_as(c_double_p),
                 ia.ctypes.data_as(c_int_p), ja.ctypes.data_as(c_int_p))
     return A, (ia, ja, val)
+
+
+def as_str(nx, ny, nz, nc, offsets, diag, bands):
+    """Wrap numpy arrays in a dSTRmat: diag of ngrid*nc*nc doubles, bands[b] of (ngrid - |offsets[b]|)*nc*nc doubles
+    (a lower band indexed by its column).  Returns (struct, keepalive)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    diag = np.ascontiguousarray(diag, dtype=np.float64).reshape(-1)
+    bands = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1) for b in bands]
+    ngrid = nx * ny * nz
+    assert diag.size == ngrid * nc * nc and len(bands) == len(offsets)
+    for o, b in zip(offsets, bands):
+        assert b.size == max(ngrid - abs(int(o)), 0) * nc * nc
+    ptrs = (c_double_p * max(len(bands), 1))(*[b.ctypes.data_as(c_double_p) for b in bands])
+    A = dSTRmat(nx, ny, nz, nx * ny, nc, ngrid, diag.ctypes.data_as(c_double_p), len(bands),
+                offsets.ctypes.data_as(c_int_p), C.cast(ptrs, C.POINTER(c_double_p)))
+    return A, (offsets, diag, bands, ptrs)
 
 
 def as_vec(x):

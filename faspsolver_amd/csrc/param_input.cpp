@@ -436,6 +436,45 @@ int fasp_dbsr_read(const char* filename, dBSRmat* A)
     return FASP_SUCCESS;
 }
 
+// BlaIO.c:699: "nx ny nz / nc / nband / n diag(n) / offset n band(n)" for each band.  The lengths the file states must be those of the
+// format (ngrid*nc*nc, (ngrid - |offset|)*nc*nc), where the reference allocates whatever they say.
+int fasp_dstr_read(const char* filename, dSTRmat* A)
+{
+    if (!filename || !A) return ERROR_INPUT_PAR;
+    File f(filename);
+    if (!f.fp) return ERROR_OPEN_FILE;
+    std::printf("%s: reading file %s ...\n", __func__, filename);
+    int nx, ny, nz, nc, nband, n;
+    if (skip_comments(f.fp) < 0 || fscanf(f.fp, "%d %d %d", &nx, &ny, &nz) != 3 || fscanf(f.fp, "%d", &nc) != 1 ||
+        fscanf(f.fp, "%d", &nband) != 1 || nx <= 0 || ny <= 0 || nz <= 0 || nc <= 0 || nband < 0 ||
+        (long long)nx * ny * nz * nc * nc > 0x7fffffffLL)
+        return ERROR_WRONG_FILE;
+    const int ngrid = nx * ny * nz, nc2 = nc * nc;
+    A->nx = nx; A->ny = ny; A->nz = nz; A->nxy = nx * ny; A->ngrid = ngrid; A->nc = nc; A->nband = nband;
+    A->offsets = static_cast<int*>(std::calloc((size_t)std::max(nband, 1), sizeof(int)));
+    A->offdiag = static_cast<double**>(std::calloc((size_t)std::max(nband, 1), sizeof(double*)));
+    A->diag = static_cast<double*>(std::calloc((size_t)ngrid * nc2, sizeof(double)));
+    auto fail = [&]() {
+        for (int b = 0; b < nband; ++b) std::free(A->offdiag[b]);
+        std::free(A->offsets); std::free(A->offdiag); std::free(A->diag);
+        A->offsets = nullptr; A->offdiag = nullptr; A->diag = nullptr;
+        A->nx = A->ny = A->nz = A->nxy = A->ngrid = A->nc = A->nband = 0;
+        return ERROR_WRONG_FILE;
+    };
+    if (fscanf(f.fp, "%d", &n) != 1 || n != ngrid * nc2) return fail();
+    for (int i = 0; i < n; ++i) if (fscanf(f.fp, "%le", &A->diag[i]) != 1) return fail();
+    for (int b = 0; b < nband; ++b) {
+        int offset;
+        if (fscanf(f.fp, "%d %d", &offset, &n) != 2) return fail();
+        const long long len = std::max(0LL, (long long)ngrid - std::llabs((long long)offset)) * nc2;
+        if ((long long)n != len) return fail();
+        A->offsets[b] = offset;
+        A->offdiag[b] = static_cast<double*>(std::calloc((size_t)std::max(n, 1), sizeof(double)));
+        for (int i = 0; i < n; ++i) if (fscanf(f.fp, "%le", &A->offdiag[b][i]) != 1) return fail();
+    }
+    return FASP_SUCCESS;
+}
+
 namespace {
 // The coordinate-format readers of BlaIO.c share one body: "m n nnz" then nnz triples "i j value";
 // they differ in the index base and in whether the file holds one triangle of a symmetric matrix.

@@ -165,6 +165,7 @@ static inline int vec_grid(int n)
 }  // namespace fasp
 
 #include "bsr.hip.h"
+#include "str.hip.h"
 
 // ===========================================================================
 // C ABI
@@ -1209,12 +1210,12 @@ bool same_host_matrix(const HostCSR& M, const dCSRmat* A)
 
 // ---------------------------------------------------------------------------
 // The plug-in driver: every Krylov entry point with a caller's `precond` -- CSR (SolCSR.c), BSR (SolBSR.c) and
-// matrix-free (SolMatFree.c) -- is this one function.  What the three families do differently is a KFamily.
+// structured (SolSTR.c) and matrix-free (SolMatFree.c) -- is this one function.  What the families do differently is a KFamily.
 // ---------------------------------------------------------------------------
 struct PcState;
 // Each field mirrors what the family's own function did before the three were merged; none of them is a choice made here.
 struct KFamily {
-    const char* fmt;             // K.fmt, the "(%s)" of the solvers' first line: "CSR" / "BSR" / "MatFree", as today
+    const char* fmt;             // K.fmt, the "(%s)" of the solvers' first line: "CSR" / "BSR" / "STR" / "MatFree", as today
     bool ctx_first;              // ctx_init() before the argument checks, failure -> die_no_device (BSR: after them, via TmpBSR)
     bool bad_bsr_dies;           // a BSR operator that cannot be uploaded -> die_bsr (matrix-free: ERROR_ALLOC_MEM), as today
     bool refuse_multi_rank;      // comm_size() > 1 -> ERROR_INPUT_PAR; the BSR family has never checked
@@ -1285,10 +1286,32 @@ bool bind_diag_bsr(precond* pc, int n, int nb, PcState& S, KOps& K, int* st)
     };
     return true;
 }
+// block-diagonal preconditioner of a structured matrix (PreSTR.c:44): z_i = Dinv_i r_i on the device
+bool bind_diag_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
+{
+    if (!(pc && pc->fct == fasp_precond_dstr_diag && pc->data)) return false;
+    const precond_diag_str* d = static_cast<const precond_diag_str*>(pc->data);
+    if (d->nc != nc || d->diag.row != n * nc || !d->diag.val) return false;
+    S.ddiag.reset(new TmpVec(d->diag.val, (size_t)n * nc));
+    const double* dd = S.ddiag->d;
+    double* zz = S.out(n);
+    if (!dd || !zz) { *st = ERROR_ALLOC_MEM; return true; }
+    K.pc = [dd, zz, n, nc](double* in, double** out) {
+        hipLaunchKernelGGL(k_str_dinv_apply, dim3(vec_grid(n)), dim3(BLOCK), 0, g_ctx.stream, n, nc, dd, (const double*)in, zz);
+        *out = zz;
+        return 0;
+    };
+    return true;
+}
+// the structured family knows no device AMG handle and no ILU factor (the reference's STR ILU is a format of its own)
+int find_amg_none(precond*, int, PcState&) { return FASP_SUCCESS; }
+IluDev* ilu_lookup_none(precond*, int, std::unique_ptr<IluDev, void (*)(IluDev*)>&, int* which, int* st) { *which = -1; *st = FASP_SUCCESS; return nullptr; }
+constexpr unsigned K_OFFER_STR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_MinRes);
 
 //                              fmt        ctx_first bad_bsr_dies refuse_multi_rank refuse_empty find_amg          borrow_resident fused_mxv_dot bind_diag      ilu_lookup          handle_ilu_checked mf_texts offered
 const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_diag_csr, ilu_of_precond,     false,             false,   K_OFFER_ALL};
 const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR};
+const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_diag_str, ilu_lookup_none,    false,             false,   K_OFFER_STR};
 const KFamily FAMILY_MATFREE = {"MatFree", true,     false,       true,             true,        find_amg_matfree, false,          false,        nullptr,       ilu_of_precond,     false,             true,    K_OFFER_MATFREE};
 
 // K.pc for the caller's `precond`: a device AMG handle (S.h / S.hb, found by F.find_amg), a device ILU, a device (block-)
@@ -1324,19 +1347,21 @@ int bind_precond(const KFamily& F, precond* pc, int n, int nb, PcState& S, KOps&
     return st;
 }
 
-// where the operator comes from: a host dCSRmat, a host dBSRmat, or an mxv_matfree -- which is one of the two when
+// where the operator comes from: a host dCSRmat, a host dBSRmat, a host dSTRmat, or an mxv_matfree -- which is one of the three when
 // fasp_solver_matfree_init installed it (recognised by its function pointer), else a host callback
 struct KOperator {
-    enum Kind { CSR, BSR, HOST } kind;
+    enum Kind { CSR, BSR, STR, HOST } kind;
     const void* A;
     const mxv_matfree* mf = nullptr;
     bool valid = true;
     KOperator(const dCSRmat* M) : kind(CSR), A(M) {}
     KOperator(const dBSRmat* M) : kind(BSR), A(M) {}
+    KOperator(const dSTRmat* M) : kind(STR), A(M) {}
     KOperator(const mxv_matfree* m) : kind(HOST), A(nullptr), mf(m), valid(m && m->fct)
     {
         if (valid && m->fct == fasp_hip_mxv_csr) { kind = CSR; A = m->data; }
         if (valid && m->fct == fasp_hip_mxv_bsr) { kind = BSR; A = m->data; }
+        if (valid && m->fct == fasp_hip_mxv_str) { kind = STR; A = m->data; }
     }
 };
 
@@ -1346,11 +1371,13 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
     if (F.ctx_first && ctx_init() < 0) die_no_device(fn);
     const dCSRmat* Ac = op.kind == KOperator::CSR ? static_cast<const dCSRmat*>(op.A) : nullptr;
     const dBSRmat* Ab = op.kind == KOperator::BSR ? static_cast<const dBSRmat*>(op.A) : nullptr;
+    const dSTRmat* As = op.kind == KOperator::STR ? static_cast<const dSTRmat*>(op.A) : nullptr;
     if (!op.valid || !b || !u || (op.kind != KOperator::HOST && !op.A)) return ERROR_INPUT_PAR;
     const int n = b->row;
     if (u->row != n || (F.refuse_empty && n <= 0)) return ERROR_INPUT_PAR;
     if (Ac && (Ac->row != Ac->col || Ac->row != n)) return ERROR_INPUT_PAR;
     if (Ab && (Ab->ROW != Ab->COL || Ab->ROW * Ab->nb != n)) return ERROR_INPUT_PAR;
+    if (As && (str_plan(As, nullptr) < 0 || As->ngrid * As->nc != n)) return ERROR_INPUT_PAR;
     if (F.refuse_multi_rank && comm_size() > 1) return ERROR_INPUT_PAR;  // plug-in level: one GPU
     PcState S;
     int st = F.find_amg(pc, n, S);
@@ -1363,6 +1390,7 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
     K.halo = [](double*) { return 0; };
     std::unique_ptr<TmpCSR> csr;
     std::unique_ptr<TmpBSR> bsr;
+    std::unique_ptr<TmpSTR> str;
     std::unique_ptr<TmpVec> dy;
     std::vector<double> hx, hy;
     if (Ac) {
@@ -1386,6 +1414,12 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
         const TmpBSR* Mp = bsr.get();
         K.mxv = [Mp](const double* x, double* y) { bsr_mxv(*Mp, x, y); };
         K.resid = [Mp](const double* x, const double* bb, double* r) { bsr_resid(*Mp, x, bb, r); };
+    } else if (As) {
+        str.reset(new TmpSTR(As));
+        if (!str->ok) return ERROR_ALLOC_MEM;
+        const TmpSTR* Mp = str.get();
+        K.mxv = [Mp](const double* x, double* y) { str_mxv(*Mp, x, y); };
+        K.resid = [Mp](const double* x, const double* bb, double* r) { str_resid(*Mp, x, bb, r); };
     } else {   // a host callback: its vectors are staged through host memory once per application
         hx.resize((size_t)n); hy.resize((size_t)n);
         dy.reset(new TmpVec(nullptr, (size_t)n));
@@ -1413,7 +1447,7 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
     if (method == K_CG && !F.mf_texts)
         for (auto& v : cgv) { v.reset(new TmpVec(nullptr, (size_t)n)); if (!v->d) return ERROR_ALLOC_MEM; }
     double* const sp = cgv[0] ? cgv[0]->d : nullptr, *const stv = cgv[1] ? cgv[1]->d : nullptr, *const sr = cgv[2] ? cgv[2]->d : nullptr;
-    if ((st = bind_precond(F, pc, n, Ab ? Ab->nb : 1, S, K)) < 0) return st;
+    if ((st = bind_precond(F, pc, n, Ab ? Ab->nb : As ? As->nc : 1, S, K)) < 0) return st;
     Hist   H{nullptr, 0, 0};
     PcgOut po{BIGREAL, BIGREAL, BIGREAL};
     st = krylov_run(K, method, F.offered, F.mf_texts, P, db.d, du.d, sp, stv, sr, &H, &po);
@@ -1682,10 +1716,12 @@ int fasp_solver_dbsr_krylov_diag(dBSRmat* A, dvector* b, dvector* x, ITS_param* 
     return status;
 }
 
+#include "str_api.hip.h"
+
 // ---------------------------------------------------------------------------
 // Matrix-free interface of the reference (fasp.h:1109 mxv_matfree, SolMatFree.c): Krylov methods
 // that see the operator only as y = A x.  An operator installed by fasp_solver_matfree_init
-// (MAT_CSR / MAT_BSR) is recognised by its function pointer: the matrix is uploaded once and the
+// (MAT_CSR / MAT_BSR / MAT_STR) is recognised by its function pointer: the matrix is uploaded once and the
 // whole iteration stays in HBM.  Any other mf->fct is a host callback: its vectors are staged
 // through host memory once per application (as for foreign preconditioners).
 // ---------------------------------------------------------------------------
@@ -1699,6 +1735,11 @@ void fasp_hip_mxv_bsr(const void* A, const double* x, double* y)  // SolMatFree.
     FASP_ENTRY();
     fasp_blas_dbsr_mxv(static_cast<const dBSRmat*>(A), x, y);
 }
+void fasp_hip_mxv_str(const void* A, const double* x, double* y)  // SolMatFree.c: fasp_blas_mxv_str
+{
+    FASP_ENTRY();
+    fasp_blas_dstr_mxv(static_cast<const dSTRmat*>(A), x, y);
+}
 
 // SolMatFree.c:201
 void fasp_solver_matfree_init(int matrix_format, mxv_matfree* mf, void* A)
@@ -1707,7 +1748,8 @@ void fasp_solver_matfree_init(int matrix_format, mxv_matfree* mf, void* A)
     switch (matrix_format) {
         case MAT_CSR: mf->fct = fasp_hip_mxv_csr; break;
         case MAT_BSR: mf->fct = fasp_hip_mxv_bsr; break;
-        default:  // the reference also knows STR / BLC / CSRL: formats this library does not have
+        case MAT_STR: mf->fct = fasp_hip_mxv_str; break;
+        default:  // the reference also knows BLC / CSRL: formats this library does not have
             std::printf("### ERROR: Unknown matrix format %d!\n", matrix_format);
             std::exit(ERROR_DATA_STRUCTURE);
     }

@@ -168,6 +168,22 @@ typedef struct dBSRmat {
     int*    JA;
 } dBSRmat;
 
+/* fasp.h:316  sizeof == 64.  Structured (banded block) matrix on an nx x ny x nz grid: ngrid = nxy * nz grid points, nc x nc
+ * blocks (row-major), a diagonal of ngrid blocks and nband off-diagonal bands.  Band b with offset d = offsets[b] holds the
+ * ngrid - |d| blocks A(i, i + d); a lower band (d < 0) is indexed by its column: offdiag[b][k] is A(k - d, k). */
+typedef struct dSTRmat {
+    int      nx;
+    int      ny;
+    int      nz;
+    int      nxy;
+    int      nc;
+    int      ngrid;
+    double*  diag;
+    int      nband;
+    int*     offsets;
+    double** offdiag;
+} dSTRmat;
+
 /* fasp.h:354  sizeof == 16 */
 typedef struct dvector {
     int     row;
@@ -338,6 +354,12 @@ typedef struct {
     dvector diag;   /* ROW inverse diagonal blocks of nb*nb doubles */
 } precond_diag_bsr;
 
+/* fasp.h:1074  data of the block-diagonal preconditioner of a dSTRmat */
+typedef struct {
+    int     nc;
+    dvector diag;   /* ngrid inverse diagonal blocks of nc*nc doubles */
+} precond_diag_str;
+
 /* fasp.h:1109  matrix-free operator: y = A x through a function pointer */
 typedef struct {
     void* data;
@@ -346,6 +368,7 @@ typedef struct {
 #define MAT_FREE 0
 #define MAT_CSR  1
 #define MAT_BSR  2
+#define MAT_STR  3
 
 /* ------------------------------------------------------------------------ */
 /* reference entry points kept by this library                              */
@@ -413,6 +436,22 @@ void   fasp_smoother_dbsr_jacobi1(dBSRmat* A, dvector* b, dvector* u, double* di
 /* mean milliseconds per launch of the BSR SpMV kernel on a resident copy of A (HIP events) */
 double fasp_hip_time_bsr_mxv(const dBSRmat* A, int reps);
 
+/* Structured (STR) matrices, BlaSparseSTR.c:41-162, BlaFormat.c:119, BlaSpmvSTR.c:61/:131 -- the reference's third Krylov format.
+ * create / alloc / free / cp / fasp_format_dstr_dcsr are host code (no GPU needed; arrays from fasp_mem_calloc, B's CSR arrays
+ * are released with fasp_dcsr_free; fasp_dstr_cp copies into an allocated B as the reference does).  The two products take host
+ * vectors of ngrid*nc doubles and run k_str_band on the device: no column indices, and the reference's result bit for bit in each of
+ * its four arithmetic forms.  fasp_blas_dstr_mxv clears and writes exactly ngrid*nc entries of y (the reference
+ * clears ngrid*nc*nc, BlaSpmvSTR.c:135).  A matrix with nc outside 1..7, nband < 0, an offset of 0 or a repeated offset: message and
+ * exit(ERROR_INPUT_PAR); a band with |offset| >= ngrid is legal and empty. */
+dSTRmat fasp_dstr_create(const int nx, const int ny, const int nz, const int nc, const int nband, int* offsets);
+void    fasp_dstr_alloc(const int nx, const int ny, const int nz, const int nxy, const int ngrid, const int nband,
+                        const int nc, int* offsets, dSTRmat* A);
+void    fasp_dstr_free(dSTRmat* A);
+void    fasp_dstr_cp(const dSTRmat* A, dSTRmat* B);
+short   fasp_format_dstr_dcsr(const dSTRmat* A, dCSRmat* B);
+void    fasp_blas_dstr_aAxpy(const double alpha, const dSTRmat* A, const double* x, double* y);
+void    fasp_blas_dstr_mxv(const dSTRmat* A, const double* x, double* y);
+
 /* ini front-end: fasp_param_input (AuxInput.c:86) + fasp_param_init (AuxParam.c:34) for the two parameter
  * structs of this path -- same keywords, value formats, defaults and range check as the reference's
  * ini files (test/ini/, .dat).  fname == NULL: defaults.  Returns 0, ERROR_OPEN_FILE (-10) or
@@ -424,6 +463,8 @@ int  fasp_hip_param_input(const char* fname, ITS_param* itsparam, AMG_param* amg
 int  fasp_dcsrvec_read2(const char* filemat, const char* filerhs, dCSRmat* A, dvector* b);
 int  fasp_dvec_read(const char* filename, dvector* b);
 int  fasp_dbsr_read(const char* filename, dBSRmat* A);
+/* BlaIO.c:699: "nx ny nz / nc / nband / n diag.. / offset n band.." per band; release with fasp_dstr_free */
+int  fasp_dstr_read(const char* filename, dSTRmat* A);
 /* coordinate formats (BlaIO.c:332 0-based, :384 / :514 / :567 1-based, :624 one triangle of a
  * symmetric MatrixMarket file) and the writers that pair with the readers (:1388, :1623, :1145) */
 int  fasp_dcoo_read(const char* filename, dCSRmat* A);
@@ -583,16 +624,37 @@ int  fasp_solver_dcsr_krylov_diag(dCSRmat* A, dvector* b, dvector* x, ITS_param*
 int  fasp_solver_dbsr_itsolver(dBSRmat* A, dvector* b, dvector* x, precond* pc, ITS_param* itparam);
 int  fasp_solver_dbsr_krylov(dBSRmat* A, dvector* b, dvector* x, ITS_param* itparam);
 int  fasp_solver_dbsr_krylov_diag(dBSRmat* A, dvector* b, dvector* x, ITS_param* itparam);
+/* The same for structured matrices (KryPcg.c:970, KryPbcgs.c:1027, KryPgmres.c:998, KryPvgmres.c:1116, KryPminres.c:876;
+ * SolSTR.c:51/:132/:175; PreSTR.c:44).  One GPU; the operator is uploaded once as index-free bands and the iteration stays in
+ * HBM.  fasp_precond_dstr_diag (data: precond_diag_str*) is recognised by its address and applied on the device, any other
+ * preconditioner is called on host copies.  fasp_solver_dstr_itsolver dispatches CG, BiCGstab, GMRES and VGMRES as the reference
+ * does (anything else: ERROR_SOLVER_TYPE).  ERROR_INPUT_PAR: a NULL pointer, nc outside 1..7, nband < 0, an offset of 0 or a
+ * repeated one, vectors of another length than ngrid*nc, more than one rank. */
+void fasp_precond_dstr_diag(double* r, double* z, void* data);
+int  fasp_solver_dstr_pcg(dSTRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
+                          const int MaxIt, const short StopType, const short PrtLvl);
+int  fasp_solver_dstr_pbcgs(dSTRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
+                            const int MaxIt, const short StopType, const short PrtLvl);
+int  fasp_solver_dstr_pminres(dSTRmat* A, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
+                              const int MaxIt, const short StopType, const short PrtLvl);
+int  fasp_solver_dstr_pgmres(dSTRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
+                             const int MaxIt, const short restart, const short StopType, const short PrtLvl);
+int  fasp_solver_dstr_pvgmres(dSTRmat* A, dvector* b, dvector* x, precond* pc, const double tol, const double abstol,
+                              const int MaxIt, const short restart, const short StopType, const short PrtLvl);
+int  fasp_solver_dstr_itsolver(dSTRmat* A, dvector* b, dvector* x, precond* pc, ITS_param* itparam);
+int  fasp_solver_dstr_krylov(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam);
+int  fasp_solver_dstr_krylov_diag(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam);
 
 /* Matrix-free interface (SolMatFree.c:58/:157/:201; KryPcg.c:1260, KryPbcgs.c:1349, KryPgcg.c:213,
  * KryPgmres.c:1309, KryPvgmres.c:1468, KryPvfgmres.c:1026, KryPminres.c:1283 -- the reference keeps older texts of
- * CG, GMRES and MinRes for this interface; they are what runs here).  fasp_solver_matfree_init(MAT_CSR | MAT_BSR)
- * installs fasp_hip_mxv_csr / _bsr: such an operator is uploaded once and the iteration stays in HBM.
+ * CG, GMRES and MinRes for this interface; they are what runs here).  fasp_solver_matfree_init(MAT_CSR | MAT_BSR | MAT_STR)
+ * installs fasp_hip_mxv_csr / _bsr / _str: such an operator is uploaded once and the iteration stays in HBM.
  * Any other mf->fct is called as a host function on host copies (one PCIe round trip per product).
  * fasp_solver_pminres: the reference's restart branches skip the preconditioner when one is given and dereference
  * pc == NULL otherwise (KryPminres.c:1524, :1605); here both cases take tz = tp there (krylov.hip.h). */
 void fasp_hip_mxv_csr(const void* A, const double* x, double* y);
 void fasp_hip_mxv_bsr(const void* A, const double* x, double* y);
+void fasp_hip_mxv_str(const void* A, const double* x, double* y);   /* MAT_STR: a dSTRmat, treated like the two above */
 void fasp_solver_matfree_init(int matrix_format, mxv_matfree* mf, void* A);
 int  fasp_solver_pcg(mxv_matfree* mf, dvector* b, dvector* u, precond* pc, const double tol, const double abstol,
                      const int MaxIt, const short StopType, const short PrtLvl);

@@ -212,6 +212,12 @@ int  fasp_hip_bsr_sweep(const dBSRmat* A, const double* b, double* u, const doub
  * tier 1, steps of tier 2}.  A NULL pointer, row != col, form outside 0 .. 2, a seq entry out of range or repeated: ERROR_INPUT_PAR, nothing
  * is touched; no usable device: ERROR_MISC; a poll of the dataflow / chain form that ran out: ERROR_MISC (and the report of seq_err_check). */
 int  fasp_hip_csr_sweep(const dCSRmat* A, const int* seq, int ns, int form, double w, int zero_start, const double* b, double* u, int* info);
+/* which arithmetic form the products of a structured matrix take (pure host code): 0 S (nc = 1, canonical offsets), 1 B (nc = 3, 5,
+ * canonical), 2 N (nc = 2, 4, 6, 7, canonical), 3 G (the reference's generic path: any other nband, a canonical count with other
+ * offsets, a grid too small for the reference's row segments); ERROR_INPUT_PAR for a matrix the library refuses. */
+int  fasp_hip_str_form(const dSTRmat* A);
+/* mean milliseconds per launch of the band SpMV kernel on a resident copy of A (HIP events); -1: no device or a refused matrix */
+double fasp_hip_time_str_mxv(const dSTRmat* A, int reps);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
