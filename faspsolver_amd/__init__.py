@@ -63,6 +63,8 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_blas_dstr_aAxpy", "fasp_blas_dstr_mxv", "fasp_precond_dstr_diag", "fasp_solver_dstr_pcg", "fasp_solver_dstr_pbcgs",
     "fasp_solver_dstr_pminres", "fasp_solver_dstr_pgmres", "fasp_solver_dstr_pvgmres", "fasp_solver_dstr_itsolver",
     "fasp_solver_dstr_krylov", "fasp_solver_dstr_krylov_diag", "fasp_hip_mxv_str", "fasp_hip_str_form", "fasp_hip_time_str_mxv",
+    "fasp_ilu_dstr_setup0", "fasp_ilu_dstr_setup1", "fasp_precond_dstr_ilu0", "fasp_precond_dstr_ilu1", "fasp_solver_dstr_krylov_ilu",
+    "fasp_hip_str_ilu_form", "fasp_hip_str_ilu_apply", "fasp_hip_time_str_ilu",
 ]
 
 
@@ -303,6 +305,20 @@ def lib():
     L.fasp_solver_dstr_krylov_diag.argtypes = L.fasp_solver_dstr_krylov.argtypes
     L.fasp_hip_mxv_str.argtypes = [C.c_void_p, T.c_double_p, T.c_double_p]
     L.fasp_hip_mxv_str.restype = None
+    # structured ILU(0) / ILU(1)
+    L.fasp_ilu_dstr_setup0.argtypes = [P(T.dSTRmat), P(T.dSTRmat)]
+    L.fasp_ilu_dstr_setup0.restype = None
+    L.fasp_ilu_dstr_setup1.argtypes = [P(T.dSTRmat), P(T.dSTRmat)]
+    L.fasp_ilu_dstr_setup1.restype = None
+    L.fasp_precond_dstr_ilu0.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_dstr_ilu0.restype = None
+    L.fasp_precond_dstr_ilu1.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_dstr_ilu1.restype = None
+    L.fasp_solver_dstr_krylov_ilu.argtypes = [P(T.dSTRmat), P(T.dvector), P(T.dvector), P(T.ITS_param), P(T.ILU_param)]
+    L.fasp_hip_str_ilu_form.argtypes = [P(T.dSTRmat), C.c_int]
+    L.fasp_hip_str_ilu_apply.argtypes = [P(T.dSTRmat), C.c_int, T.c_double_p, T.c_double_p]
+    L.fasp_hip_time_str_ilu.argtypes = [P(T.dSTRmat), C.c_int, C.c_int]
+    L.fasp_hip_time_str_ilu.restype = C.c_double
     return L
 
 

@@ -211,6 +211,10 @@ int bsr_diaginv(const dBSRmat* A, double* out);
 // fasp_smat_invp_nc (BlaSmallMatInv.c:508): one n x n block (n <= 8) inverted in place by pivoting Gauss-Jordan;
 // ERROR_SOLVER_EXIT on a pivot below SMALLREAL
 int smat_invp(double* a, int n);
+// fasp_smat_inv (BlaSmallMatInv.c:603): one n x n block (n <= 7) in place -- 1 / a, the closed forms for 2, 3, 4, smat_invp beyond
+int smat_inv(double* a, int n);
+// fasp_blas_smat_mul (BlaSmallMat.c:596): c = a b for n x n blocks, every entry summed left to right (n = 6: from 0.0); csrc/ilu_setup.cpp
+void smat_mul(const double* a, const double* b, double* c, int n);
 int check_supported_bsr(const ITS_param* itparam, const AMG_param* amgparam, int nb);
 
 // Parameter screening: every AMG_param / ITS_param combination without a device

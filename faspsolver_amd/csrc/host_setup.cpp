@@ -2295,6 +2295,42 @@ int block_inv_pivot(double* a, int n)
 }
 }  // namespace
 
+// fasp_smat_inv (BlaSmallMatInv.c:603) on one n x n block in place, n = 1 .. 7: closed forms for 2, 3, 4 (the identity for a
+// near-singular block), pivoting Gauss-Jordan beyond (the reference switches its 5 x 5 closed form off: `case -5`)
+int smat_inv(double* a, int nb)
+{
+    if (nb == 1) {
+        a[0] = 1.0 / a[0];
+    } else if (nb == 4) {
+        block_inv4(a);
+    } else if (nb > 4) {
+        return block_inv_pivot(a, nb);
+    } else if (nb == 2) {  // fasp_smat_inv_nc2, BlaSmallMatInv.c:33
+        const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+        const double det = a0 * a3 - a1 * a2;
+        if (std::fabs(det) < SMALLREAL) { a[0] = 1.0; a[1] = 0.0; a[2] = 0.0; a[3] = 1.0; }
+        else {
+            const double det_inv = 1.0 / det;
+            a[0] = a3 * det_inv; a[1] = -a1 * det_inv; a[2] = -a2 * det_inv; a[3] = a0 * det_inv;
+        }
+    } else {  // fasp_smat_inv_nc3, BlaSmallMatInv.c:67
+        const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], a6 = a[6], a7 = a[7], a8 = a[8];
+        const double M0 = a4 * a8 - a5 * a7, M3 = a2 * a7 - a1 * a8, M6 = a1 * a5 - a2 * a4;
+        const double M1 = a5 * a6 - a3 * a8, M4 = a0 * a8 - a2 * a6, M7 = a2 * a3 - a0 * a5;
+        const double M2 = a3 * a7 - a4 * a6, M5 = a1 * a6 - a0 * a7, M8 = a0 * a4 - a1 * a3;
+        const double det = a0 * M0 + a3 * M3 + a6 * M6;
+        if (std::fabs(det) < SMALLREAL) {
+            a[0] = 1.0; a[1] = 0.0; a[2] = 0.0; a[3] = 0.0; a[4] = 1.0; a[5] = 0.0; a[6] = 0.0; a[7] = 0.0; a[8] = 1.0;
+        } else {
+            const double det_inv = 1.0 / det;
+            a[0] = M0 * det_inv; a[1] = M3 * det_inv; a[2] = M6 * det_inv;
+            a[3] = M1 * det_inv; a[4] = M4 * det_inv; a[5] = M7 * det_inv;
+            a[6] = M2 * det_inv; a[7] = M5 * det_inv; a[8] = M8 * det_inv;
+        }
+    }
+    return FASP_SUCCESS;
+}
+
 int bsr_diaginv(const dBSRmat* A, double* out)
 {
     if (!A || A->nb < 1 || A->nb > 7) return ERROR_INPUT_PAR;
@@ -2305,35 +2341,7 @@ int bsr_diaginv(const dBSRmat* A, double* out)
         for (int e = 0; e < nb2; ++e) a[e] = 0.0;
         for (int k = A->IA[i]; k < A->IA[i + 1]; ++k)
             if (A->JA[k] == i) std::memcpy(a, A->val + (size_t)k * nb2, sizeof(double) * nb2);
-        if (nb == 1) {
-            a[0] = 1.0 / a[0];
-        } else if (nb == 4) {
-            block_inv4(a);
-        } else if (nb > 4) {   // fasp_smat_inv's default branch (the nc5 closed form is switched off there: `case -5`)
-            (void)block_inv_pivot(a, nb);
-        } else if (nb == 2) {  // fasp_smat_inv_nc2, BlaSmallMatInv.c:33
-            const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-            const double det = a0 * a3 - a1 * a2;
-            if (std::fabs(det) < SMALLREAL) { a[0] = 1.0; a[1] = 0.0; a[2] = 0.0; a[3] = 1.0; }
-            else {
-                const double det_inv = 1.0 / det;
-                a[0] = a3 * det_inv; a[1] = -a1 * det_inv; a[2] = -a2 * det_inv; a[3] = a0 * det_inv;
-            }
-        } else {  // fasp_smat_inv_nc3, BlaSmallMatInv.c:67
-            const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], a6 = a[6], a7 = a[7], a8 = a[8];
-            const double M0 = a4 * a8 - a5 * a7, M3 = a2 * a7 - a1 * a8, M6 = a1 * a5 - a2 * a4;
-            const double M1 = a5 * a6 - a3 * a8, M4 = a0 * a8 - a2 * a6, M7 = a2 * a3 - a0 * a5;
-            const double M2 = a3 * a7 - a4 * a6, M5 = a1 * a6 - a0 * a7, M8 = a0 * a4 - a1 * a3;
-            const double det = a0 * M0 + a3 * M3 + a6 * M6;
-            if (std::fabs(det) < SMALLREAL) {
-                a[0] = 1.0; a[1] = 0.0; a[2] = 0.0; a[3] = 0.0; a[4] = 1.0; a[5] = 0.0; a[6] = 0.0; a[7] = 0.0; a[8] = 1.0;
-            } else {
-                const double det_inv = 1.0 / det;
-                a[0] = M0 * det_inv; a[1] = M3 * det_inv; a[2] = M6 * det_inv;
-                a[3] = M1 * det_inv; a[4] = M4 * det_inv; a[5] = M7 * det_inv;
-                a[6] = M2 * det_inv; a[7] = M5 * det_inv; a[8] = M8 * det_inv;
-            }
-        }
+        (void)smat_inv(a, nb);
     }
     return FASP_SUCCESS;
 }

@@ -436,6 +436,10 @@ const char* fact_message(int e)
 
 }  // namespace
 
+namespace fasp {
+void smat_mul(const double* a, const double* b, double* c, int n) { block_mul(a, b, c, n); }
+}
+
 extern "C" {
 
 // AuxParam.c:595

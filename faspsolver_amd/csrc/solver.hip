@@ -166,6 +166,7 @@ static inline int vec_grid(int n)
 
 #include "bsr.hip.h"
 #include "str.hip.h"
+#include "str_ilu.hip.h"
 
 // ===========================================================================
 // C ABI
@@ -1223,7 +1224,7 @@ struct KFamily {
     int  (*find_amg)(precond*, int n, PcState&);   // which `precond`s are a device AMG handle; < 0: one of another size
     bool borrow_resident;        // same_host_matrix: solve on the handle's resident level-0 operator (CSR only, as today)
     bool fused_mxv_dot;          // K.mxv_dot for a CSR operator (CSR only; the matrix-free texts never ask for it)
-    bool (*bind_diag)(precond*, int n, int nb, PcState&, KOps&, int* st);   // (block-)diagonal preconditioner on the device; none: host-staged
+    bool (*bind_diag)(precond*, int n, int nb, PcState&, KOps&, int* st);   // (block-)diagonal preconditioner on the device (STR: its ILU factors too); none: host-staged
     IluDev* (*ilu_lookup)(precond*, int n, std::unique_ptr<IluDev, void (*)(IluDev*)>&, int* which, int* st);
     bool handle_ilu_checked;     // seq_err_check() also when the handle's level 0 smooths with ILU (BSR handles only, as today)
     bool mf_texts;               // the reference's older texts (pcg_mf_device, gmres_mf_device, minres_mf_device), as today
@@ -1236,6 +1237,7 @@ struct PcState {
     fasp_hip_amg_bsr* hb = nullptr;   // ... or block
     IluDev*           ilu = nullptr;
     std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp{nullptr, ilu_dev_destroy};
+    std::unique_ptr<StrIluDev> strilu;   // structured ILU factor, uploaded for this solve
     std::unique_ptr<TmpVec> ddiag, dz;   // device diagonal; output of the diagonal and of a foreign preconditioner
     std::vector<double> hr, hz;          // host staging of a foreign preconditioner
     double* out(int n) { if (!dz) dz.reset(new TmpVec(nullptr, (size_t)n)); return dz->d; }
@@ -1303,7 +1305,28 @@ bool bind_diag_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
     };
     return true;
 }
-// the structured family knows no device AMG handle and no ILU factor (the reference's STR ILU is a format of its own)
+// the reference's structured ILU preconditioners (PreSTR.c:71 / :349): recognised by their address; a factor of the operator's ngrid
+// and nc that passes str_ilu_describe is uploaded once and both triangular solves run on the device (str_ilu.hip.h).  Anything
+// else about such a `precond` (another size, a coefficient between points that are no geometric neighbours) leaves it a foreign
+// host function: staged, correct and slow.
+bool bind_ilu_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
+{
+    if (!(pc && pc->data && (pc->fct == fasp_precond_dstr_ilu0 || pc->fct == fasp_precond_dstr_ilu1))) return false;
+    const dSTRmat* LU = static_cast<const dSTRmat*>(pc->data);
+    StrIluDesc D;
+    if (!str_ilu_describe(LU, pc->fct == fasp_precond_dstr_ilu1 ? 1 : 0, D, nullptr) || D.nc != nc || D.ngrid * D.nc != n) return false;
+    S.strilu.reset(new StrIluDev(LU, D));
+    if (!S.strilu->ok) { *st = ERROR_ALLOC_MEM; return true; }
+    StrIluDev* M = S.strilu.get();
+    K.pc = [M](double* in, double** out) { *out = M->z; return str_ilu_apply(*M, in, M->z); };
+    return true;
+}
+// the structured family's device preconditioners: its ILU factors (a format of their own: no IluDev) and the block diagonal
+bool bind_pc_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
+{
+    return bind_ilu_str(pc, n, nc, S, K, st) || bind_diag_str(pc, n, nc, S, K, st);
+}
+// the structured family knows no device AMG handle and no MSR factor (its ILU is bound by bind_ilu_str)
 int find_amg_none(precond*, int, PcState&) { return FASP_SUCCESS; }
 IluDev* ilu_lookup_none(precond*, int, std::unique_ptr<IluDev, void (*)(IluDev*)>&, int* which, int* st) { *which = -1; *st = FASP_SUCCESS; return nullptr; }
 constexpr unsigned K_OFFER_STR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_MinRes);
@@ -1311,7 +1334,7 @@ constexpr unsigned K_OFFER_STR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) |
 //                              fmt        ctx_first bad_bsr_dies refuse_multi_rank refuse_empty find_amg          borrow_resident fused_mxv_dot bind_diag      ilu_lookup          handle_ilu_checked mf_texts offered
 const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_diag_csr, ilu_of_precond,     false,             false,   K_OFFER_ALL};
 const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR};
-const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_diag_str, ilu_lookup_none,    false,             false,   K_OFFER_STR};
+const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_pc_str,   ilu_lookup_none,    false,             false,   K_OFFER_STR};
 const KFamily FAMILY_MATFREE = {"MatFree", true,     false,       true,             true,        find_amg_matfree, false,          false,        nullptr,       ilu_of_precond,     false,             true,    K_OFFER_MATFREE};
 
 // K.pc for the caller's `precond`: a device AMG handle (S.h / S.hb, found by F.find_amg), a device ILU, a device (block-)
@@ -1453,7 +1476,7 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
     st = krylov_run(K, method, F.offered, F.mf_texts, P, db.d, du.d, sp, stv, sr, &H, &po);
     du.get(u->val);
     // a single-launch ILU solve (of the preconditioner, or of a block handle's cycle) that timed out
-    if ((S.ilu || (F.handle_ilu_checked && S.hb && S.hb->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
+    if ((S.ilu || (S.strilu && S.strilu->used_pipe) || (F.handle_ilu_checked && S.hb && S.hb->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
     return st;
 }
 }  // namespace
@@ -2171,7 +2194,9 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "seq_flow")) { g_tune.seq_flow = value; if (value) g_flow_disabled = false; }
     else if (!std::strcmp(key, "ilu_smooth_fused")) g_tune.ilu_smooth_fused = value;   // ILU step of the block cycle: 1 (default) the U solve writes x = x + z itself, 0 a separate axpy pass -- same bits
     else if (!std::strcmp(key, "ilu_form")) g_tune.ilu_form = value;   // ILU triangular solves: -1 (default) by the schedule's depth, 0 one launch per level, 1 one launch
-    else if (!std::strcmp(key, "seq_strip_kb")) g_tune.seq_strip_kb = value;   // KB of lower entries per strip of the dataflow solve (0, default: 256 / 512 / 1024 by level shape, seq_sched.cpp)
+    else if (!std::strcmp(key, "str_ilu_form")) g_tune.str_ilu_form = value;   // structured ILU solves (str_ilu_plan): -1 (default) by the plan, 0 one launch per level, 1 planes pipelined over workgroups (3-D)
+    else if (!std::strcmp(key, "str_ilu_wgs")) g_tune.str_ilu_wgs = value;     // workgroups of the pipelined form at most (0, default: twice the compute units)
+    else if (!std::strcmp(key, "seq_strip_kb")) g_tune.seq_strip_kb = value;  // KB of lower entries per strip of the dataflow solve (0, default: 256 / 512 / 1024 by level shape, seq_sched.cpp)
     else if (!std::strcmp(key, "seq_jobs")) g_tune.seq_jobs = value;
     else if (!std::strcmp(key, "local_square")) g_tune.local_square = value;   // a rank's rows of a partitioned level are coded like a square operator (read at upload)
     else if (!std::strcmp(key, "seq_grid")) g_tune.seq_grid = value;     // workgroups of the dataflow solve at most (0: twice the strips the chain front is in at a time + 2, seq_sched.cpp; < 0: as many as are resident)

@@ -644,6 +644,23 @@ int  fasp_solver_dstr_pvgmres(dSTRmat* A, dvector* b, dvector* x, precond* pc, c
 int  fasp_solver_dstr_itsolver(dSTRmat* A, dvector* b, dvector* x, precond* pc, ITS_param* itparam);
 int  fasp_solver_dstr_krylov(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam);
 int  fasp_solver_dstr_krylov_diag(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam);
+/* Structured ILU(0) / ILU(1).  fasp_ilu_dstr_setup0 / _setup1 (BlaILUSetupSTR.c:38 / :333) are host
+ * code (no GPU needed): LU is allocated with fasp_mem_calloc, released with fasp_dstr_free, and equals the reference's factor
+ * byte for byte for nc 1 .. 7.  A has 4 bands {+-1, +-nline} on a 2-D grid or 6 bands {+-1, +-nline, +-nplane} on a 3-D one;
+ * setup0 takes them in any storage order and always labels LU with the canonical order -1, +1, -nline, +nline, -nplane, +nplane,
+ * setup1 takes the canonical order only.  Refused, with a message and LU zeroed (null arrays, ngrid 0): another nband, another
+ * offset, nline < 2 or a grid of one line, nc outside 1 .. 7.
+ * fasp_precond_dstr_ilu0 / _ilu1 (PreSTR.c:71 / :349; data: the dSTRmat LU) are host functions too.  Handed to an STR Krylov
+ * method they are recognised by their address: the factor is uploaded once per solve and both triangular solves run on the
+ * device (k_str_tri) with the reference's result.  A factor with a non-zero coefficient between grid points that are not
+ * geometric neighbours (no grid-derived matrix has one) is applied through the host function instead.
+ * fasp_solver_dstr_krylov_ilu (SolSTR.c:236): ILU_lfil 0 or 1 (else the reference's message and ERROR_MISC), setup, solve, LU
+ * freed; a refused setup returns ERROR_INPUT_PAR. */
+void fasp_ilu_dstr_setup0(dSTRmat* A, dSTRmat* LU);                 /* BlaILUSetupSTR.c:38 */
+void fasp_ilu_dstr_setup1(dSTRmat* A, dSTRmat* LU);                 /* BlaILUSetupSTR.c:333 */
+void fasp_precond_dstr_ilu0(double* r, double* z, void* data);      /* PreSTR.c:71 */
+void fasp_precond_dstr_ilu1(double* r, double* z, void* data);      /* PreSTR.c:349 */
+int  fasp_solver_dstr_krylov_ilu(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam);   /* SolSTR.c:236 */
 
 /* Matrix-free interface (SolMatFree.c:58/:157/:201; KryPcg.c:1260, KryPbcgs.c:1349, KryPgcg.c:213,
  * KryPgmres.c:1309, KryPvgmres.c:1468, KryPvfgmres.c:1026, KryPminres.c:1283 -- the reference keeps older texts of
@@ -746,7 +763,7 @@ void fasp_smoother_dcsr_L1diag(dvector* u, const int i_1, const int i_n, const i
  * ILU as a smoother of the block AMG cycle: AMG_param.ILU_levels > 0 with fasp_solver_dbsr_krylov_amg, the fasp_hip_bsr_*
  * handles and fasp_hip_bsr_precond_setup factors the levels below ILU_levels on the host (PreAMGSetupUABSR.c:149-179) and
  * smooths them on the device with one ILU step + block Gauss-Seidel sweeps (PreMGCycle.c:321-326); one GPU only.  The
- * scalar AMG cycle (fasp_solver_dcsr_krylov_amg with ILU_levels > 0), structured ILU and Schwarz stay out of scope. */
+ * scalar AMG cycle (fasp_solver_dcsr_krylov_amg with ILU_levels > 0) and Schwarz stay out of scope; structured ILU: fasp_ilu_dstr_setup0 / _setup1 above. */
 void  fasp_param_ilu_init(ILU_param* iluparam);                                     /* AuxParam.c:595 */
 void  fasp_ilu_data_create(const int iwk, const int nwork, ILU_data* iludata);      /* PreDataInit.c:411 */
 void  fasp_ilu_data_free(ILU_data* iludata);                                        /* PreDataInit.c:445 */

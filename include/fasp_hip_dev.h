@@ -218,6 +218,18 @@ int  fasp_hip_csr_sweep(const dCSRmat* A, const int* seq, int ns, int form, doub
 int  fasp_hip_str_form(const dSTRmat* A);
 /* mean milliseconds per launch of the band SpMV kernel on a resident copy of A (HIP events); -1: no device or a refused matrix */
 double fasp_hip_time_str_mxv(const dSTRmat* A, int reps);
+/* Structured ILU on the device (csrc/str_ilu.hip.h); LU: a factor of fasp_ilu_dstr_setup0 (lfil 0) or
+ * _setup1 (lfil 1).  fasp_hip_str_ilu_form (pure host code): the form str_ilu_plan chooses for it under the tune keys in force --
+ * 0 one launch per level, 1 planes pipelined over workgroups -- or -1 when the factor cannot be bound (not such a factor, or a
+ * non-zero coefficient between grid points that are not geometric neighbours; the reason goes to stdout).
+ * fasp_hip_str_ilu_apply: z = U^-1 L^-1 r once, host vectors of ngrid*nc; returns the status of the error word afterwards
+ * (ERROR_MISC after a poll that ran out), ERROR_INPUT_PAR for a factor that cannot be bound, ERROR_MISC without a device.
+ * fasp_hip_time_str_ilu: mean milliseconds per application on a resident copy (HIP events); -1: no device or not bindable.
+ * Tune keys: str_ilu_form (-1 default: by str_ilu_plan, 0 / 1 force a form where it applies), str_ilu_wgs (workgroups of the
+ * pipelined form at most; 0: default). */
+int    fasp_hip_str_ilu_form(const dSTRmat* LU, int lfil);
+int    fasp_hip_str_ilu_apply(const dSTRmat* LU, int lfil, const double* r, double* z);
+double fasp_hip_time_str_ilu(const dSTRmat* LU, int lfil, int reps);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
