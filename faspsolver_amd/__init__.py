@@ -65,6 +65,11 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_solver_dstr_krylov", "fasp_solver_dstr_krylov_diag", "fasp_hip_mxv_str", "fasp_hip_str_form", "fasp_hip_time_str_mxv",
     "fasp_ilu_dstr_setup0", "fasp_ilu_dstr_setup1", "fasp_precond_dstr_ilu0", "fasp_precond_dstr_ilu1", "fasp_solver_dstr_krylov_ilu",
     "fasp_hip_str_ilu_form", "fasp_hip_str_ilu_apply", "fasp_hip_time_str_ilu",
+    "fasp_smoother_dstr_jacobi", "fasp_smoother_dstr_jacobi1", "fasp_smoother_dstr_gs", "fasp_smoother_dstr_gs1",
+    "fasp_smoother_dstr_gs_ascend", "fasp_smoother_dstr_gs_descend", "fasp_smoother_dstr_gs_order", "fasp_smoother_dstr_gs_cf",
+    "fasp_smoother_dstr_sor", "fasp_smoother_dstr_sor1", "fasp_smoother_dstr_sor_ascend", "fasp_smoother_dstr_sor_descend",
+    "fasp_smoother_dstr_sor_order", "fasp_smoother_dstr_sor_cf",
+    "fasp_hip_str_sweep", "fasp_hip_str_sweep_form", "fasp_hip_str_sweep_levels", "fasp_hip_time_str_sweep",
 ]
 
 
@@ -319,6 +324,20 @@ def lib():
     L.fasp_hip_str_ilu_apply.argtypes = [P(T.dSTRmat), C.c_int, T.c_double_p, T.c_double_p]
     L.fasp_hip_time_str_ilu.argtypes = [P(T.dSTRmat), C.c_int, C.c_int]
     L.fasp_hip_time_str_ilu.restype = C.c_double
+    # the structured smoothers (ItrSmootherSTR.c)
+    A_, V_, D_, I_ = P(T.dSTRmat), P(T.dvector), T.c_double_p, T.c_int_p
+    for name, args in (("jacobi", []), ("jacobi1", [D_]), ("gs", [C.c_int, I_]), ("gs1", [C.c_int, I_, D_]), ("gs_ascend", [D_]),
+                       ("gs_descend", [D_]), ("gs_order", [D_, I_]), ("gs_cf", [D_, I_, C.c_int]), ("sor", [C.c_int, I_, C.c_double]),
+                       ("sor1", [C.c_int, I_, D_, C.c_double]), ("sor_ascend", [D_, C.c_double]), ("sor_descend", [D_, C.c_double]),
+                       ("sor_order", [D_, I_, C.c_double]), ("sor_cf", [D_, I_, C.c_int, C.c_double])):
+        f = getattr(L, "fasp_smoother_dstr_" + name)
+        f.argtypes = [A_, V_, V_] + args
+        f.restype = None
+    L.fasp_hip_str_sweep.argtypes = [A_, C.c_int, C.c_int, I_, C.c_double, D_, D_, D_, C.c_int, I_]
+    L.fasp_hip_str_sweep_form.argtypes = [A_, C.c_int, I_]
+    L.fasp_hip_str_sweep_levels.argtypes = [A_, C.c_int, I_, I_, I_, C.c_int]
+    L.fasp_hip_time_str_sweep.argtypes = [A_, C.c_int, C.c_int, I_, C.c_double, C.c_int]
+    L.fasp_hip_time_str_sweep.restype = C.c_double
     return L
 
 

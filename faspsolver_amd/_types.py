@@ -45,6 +45,7 @@ SMOOTHER_JACOBIF, SMOOTHER_GSF = 11, 12
 COARSE_RS, COARSE_RSP, COARSE_CR, COARSE_AC, COARSE_MIS = 1, 2, 3, 4, 5
 INTERP_DIR, INTERP_STD, INTERP_ENG, INTERP_RDC, INTERP_EXT = 1, 2, 3, 4, 6
 NO_ORDER, CF_ORDER = 0, 1
+ASCEND, DESCEND, USERDEFINED, CPFIRST, FPFIRST = 12, 21, 0, 1, -1   # the orders of the structured smoothers (fasp_smoother_dstr_*)
 MAT_FREE, MAT_CSR, MAT_BSR, MAT_STR = 0, 1, 2, 3
 
 

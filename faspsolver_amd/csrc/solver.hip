@@ -167,6 +167,7 @@ static inline int vec_grid(int n)
 #include "bsr.hip.h"
 #include "str.hip.h"
 #include "str_ilu.hip.h"
+#include "str_sweep.hip.h"
 
 // ===========================================================================
 // C ABI
@@ -2196,6 +2197,8 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "ilu_form")) g_tune.ilu_form = value;   // ILU triangular solves: -1 (default) by the schedule's depth, 0 one launch per level, 1 one launch
     else if (!std::strcmp(key, "str_ilu_form")) g_tune.str_ilu_form = value;   // structured ILU solves (str_ilu_plan): -1 (default) by the plan, 0 one launch per level, 1 planes pipelined over workgroups (3-D)
     else if (!std::strcmp(key, "str_ilu_wgs")) g_tune.str_ilu_wgs = value;     // workgroups of the pipelined form at most (0, default: twice the compute units)
+    else if (!std::strcmp(key, "str_sweep_form")) g_tune.str_sweep_form = value;   // structured GS / SOR sweeps (str_sweep_plan): -1 (default) by the plan, 0 one launch per level, 1 planes pipelined over workgroups (3-D), 2 the ordered form (level list)
+    else if (!std::strcmp(key, "str_sweep_wgs")) g_tune.str_sweep_wgs = value;     // workgroups of the pipelined sweep at most (0, default: twice the compute units)
     else if (!std::strcmp(key, "seq_strip_kb")) g_tune.seq_strip_kb = value;  // KB of lower entries per strip of the dataflow solve (0, default: 256 / 512 / 1024 by level shape, seq_sched.cpp)
     else if (!std::strcmp(key, "seq_jobs")) g_tune.seq_jobs = value;
     else if (!std::strcmp(key, "local_square")) g_tune.local_square = value;   // a rank's rows of a partitioned level are coded like a square operator (read at upload)

@@ -336,3 +336,234 @@ int fasp_solver_dstr_krylov_ilu(dSTRmat* A, dvector* b, dvector* x, ITS_param* i
     fasp_dstr_free(&LU);
     return status;
 }
+
+// ---- the smoothers: ItrSmootherSTR.c (csrc/str_sweep.hip.h) ------------------------------------------------------
+namespace {
+struct StrSweepPrep {
+    StrSweepDesc D;
+    bool bad_matrix = false;   // a matrix the library refuses (as opposed to a refused sequence or a missing diaginv)
+    bool todo = false, natural = false, cf = false, desc = false;
+    int  form = STR_SWF_LIST;
+    std::vector<int> seq;       // the visits of the ordered form
+    std::vector<double> dinv;   // the diagonal blocks inverted here
+    const double* dg = nullptr;   // what the closing step uses: A's diagonal (nc == 1) or inverted blocks
+};
+
+// Everything a sweep needs that the host decides: the dispatch of _gs1 / _sor1 (ItrSmootherSTR.c:277 / :935) on (order, mark) -- cf_entry:
+// the C/F form whatever `order` is, as the _cf entries are called --, the checks, the form (str_sweep_plan) and the visits.  fn: refusals
+// of a sequence or of a missing diaginv are reported under this name.  need_diag: resolve P.dg (invert: the blocks are inverted here
+// when diaginv is NULL, as the entries without the trailing 1 do with fasp_smat_inv).
+int str_sweep_prepare(const char* fn, const dSTRmat* A, int kind, int order, const int* mark, bool cf_entry, const double* diaginv, bool invert,
+                      bool need_diag, StrSweepPrep& P)
+{
+    if (str_sweep_describe(A, P.D) < 0 || kind < STR_SWEEP_JACOBI || kind > STR_SWEEP_SOR) { P.bad_matrix = true; return ERROR_INPUT_PAR; }
+    const int ngrid = P.D.ngrid, nc = P.D.nc;
+    if (kind == STR_SWEEP_JACOBI) { P.todo = true; P.form = STR_SWF_JACOBI; }
+    else {
+        if (cf_entry && !mark) { std::fprintf(stderr, "### ERROR: %s: the C/F order needs a mark array\n", fn); return ERROR_INPUT_PAR; }
+        P.cf = mark && (cf_entry || order != STR_ORDER_USER);
+        P.natural = !mark && (order == STR_ORDER_ASCEND || order == STR_ORDER_DESCEND);
+        P.desc = P.natural && order == STR_ORDER_DESCEND;
+        P.todo = mark || P.natural;
+        if (!P.todo) return FASP_SUCCESS;   // mark == NULL and neither ASCEND nor DESCEND: the reference does nothing
+        if (mark && !P.cf) {
+            std::vector<char> seen((size_t)std::max(ngrid, 1), 0);
+            for (int q = 0; q < ngrid; ++q) {
+                if (mark[q] < 0 || mark[q] >= ngrid || seen[(size_t)mark[q]]) {
+                    std::fprintf(stderr, "### ERROR: %s: the user-defined order is not a sequence of all %d grid points (entry %d: %d)\n", fn, ngrid, q, mark[q]);
+                    return ERROR_INPUT_PAR;
+                }
+                seen[(size_t)mark[q]] = 1;
+            }
+        }
+        P.form = str_sweep_plan(P.D, P.natural);
+        if (P.form == STR_SWF_LIST) str_sweep_visits(ngrid, order, mark, P.cf, kind == STR_SWEEP_SOR && nc == 1, P.seq);
+    }
+    if (!need_diag) return FASP_SUCCESS;
+    if (nc == 1) P.dg = A->diag;
+    else if (diaginv) P.dg = diaginv;
+    else if (invert) {
+        const size_t nc2 = (size_t)nc * nc;
+        P.dinv.assign(A->diag, A->diag + (size_t)ngrid * nc2);
+        for (int i = 0; i < ngrid; ++i) (void)smat_inv(P.dinv.data() + (size_t)i * nc2, nc);
+        P.dg = P.dinv.data();
+    } else {
+        std::fprintf(stderr, "### ERROR: %s: nc = %d needs the inverted diagonal blocks (diaginv is NULL)\n", fn, nc);
+        return ERROR_INPUT_PAR;
+    }
+    return FASP_SUCCESS;
+}
+
+// nsweeps sweeps on a resident copy, host vectors in and out.  reps > 0: `reps` further sweeps are timed with HIP events into *ms.
+int str_sweep_run(const char* fn, const dSTRmat* A, int kind, int order, const int* mark, bool cf_entry, double w, const double* diaginv, bool invert,
+                  const double* b, double* u, int nsweeps, int* info, int reps, double* ms, bool* bad_matrix)
+{
+    StrSweepPrep P;
+    const int st0 = str_sweep_prepare(fn, A, kind, order, mark, cf_entry, diaginv, invert, true, P);
+    if (bad_matrix) *bad_matrix = P.bad_matrix;
+    if (info) std::fill(info, info + 8, 0);
+    if (st0 < 0) return st0;
+    if (!P.todo || P.D.ngrid == 0 || nsweeps <= 0) return FASP_SUCCESS;
+    if (ctx_init() < 0) return ERROR_MISC;
+    StrSweepDev M(A, P.D, kind, P.form, P.desc, w, P.dg, P.seq, b, u);
+    if (!M.ok) return ERROR_ALLOC_MEM;
+    int st = FASP_SUCCESS;
+    for (int s = 0; s < nsweeps && st >= 0; ++s) st = M.sweep();
+    if (reps > 0 && st >= 0) {
+        hipEvent_t e0, e1;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return ERROR_MISC;
+        (void)hipEventRecord(e0, g_ctx.stream);
+        for (int i = 0; i < reps && st >= 0; ++i) st = M.sweep();
+        (void)hipEventRecord(e1, g_ctx.stream);
+        (void)hipEventSynchronize(e1);
+        float t = 0.f;
+        (void)hipEventElapsedTime(&t, e0, e1);
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        if (ms) *ms = (double)t / reps;
+    }
+    if (hipStreamSynchronize(g_ctx.stream) != hipSuccess && st >= 0) st = ERROR_MISC;
+    if (M.used_pipe && seq_err_check() < 0 && st >= 0) st = ERROR_MISC;   // a poll of the pipelined form that ran out
+    if (st >= 0 && hipMemcpy(u, M.u, sizeof(double) * (size_t)P.D.ngrid * P.D.nc, hipMemcpyDeviceToHost) != hipSuccess) st = ERROR_MISC;
+    if (info) {
+        info[0] = P.form; info[1] = M.launches; info[2] = M.levels; info[3] = M.wgs; info[4] = M.visits; info[5] = P.D.geo ? 1 : 0;
+    }
+    return st;
+}
+
+// the public smoothers: one-shot, host vectors, void as in the reference
+void str_smoother_public(const char* fn, dSTRmat* A, dvector* b, dvector* u, int kind, int order, int* mark, bool cf_entry, double w,
+                         double* diaginv, bool invert)
+{
+    if (!A || !b || !u || !b->val || !u->val) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", fn); return; }
+    if (A->nc < 1) { std::printf("### ERROR: nc is illegal! [%s]\n", fn); std::fflush(stdout); return; }
+    const long long n = (long long)A->ngrid * A->nc;
+    if (A->ngrid > 0 && (b->row < n || u->row < n)) { std::fprintf(stderr, "### ERROR: %s: b and u need ngrid * nc = %lld entries\n", fn, n); return; }
+    bool bad_matrix = false;
+    const int st = str_sweep_run(fn, A, kind, order, mark, cf_entry, w, diaginv, invert, b->val, u->val, 1, nullptr, 0, nullptr, &bad_matrix);
+    if (bad_matrix) die_str(fn, ERROR_INPUT_PAR);
+    if (st == ERROR_INPUT_PAR) return;   // a refused sequence or a missing diaginv: said above, u untouched
+    if (st == ERROR_MISC && !g_ctx.ready) die_str(fn, 0);
+    if (st < 0) { std::fprintf(stderr, "### ERROR: %s: sweep failed (%d)\n", fn, st); std::exit(st); }
+}
+}  // namespace
+
+void fasp_smoother_dstr_jacobi(dSTRmat* A, dvector* b, dvector* u)  // ItrSmootherSTR.c:43
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_JACOBI, 0, nullptr, false, 1.0, nullptr, true);
+}
+void fasp_smoother_dstr_jacobi1(dSTRmat* A, dvector* b, dvector* u, double* diaginv)  // :92
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_JACOBI, 0, nullptr, false, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_gs(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark)  // :217
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, order, mark, false, 1.0, nullptr, true);
+}
+void fasp_smoother_dstr_gs1(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, double* diaginv)  // :277
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, order, mark, false, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_gs_ascend(dSTRmat* A, dvector* b, dvector* u, double* diaginv)  // :322
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, STR_ORDER_ASCEND, nullptr, false, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_gs_descend(dSTRmat* A, dvector* b, dvector* u, double* diaginv)  // :438
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, STR_ORDER_DESCEND, nullptr, false, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_gs_order(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark)  // :556
+{
+    FASP_ENTRY();
+    if (!mark) { std::fprintf(stderr, "### ERROR: %s: the user-defined order needs a mark array\n", __func__); return; }
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, STR_ORDER_USER, mark, false, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_gs_cf(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, const int order)  // :680
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_GS, order, mark, true, 1.0, diaginv, false);
+}
+void fasp_smoother_dstr_sor(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, const double weight)  // :873
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, order, mark, false, weight, nullptr, true);
+}
+void fasp_smoother_dstr_sor1(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, double* diaginv, const double weight)  // :935
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, order, mark, false, weight, diaginv, false);
+}
+void fasp_smoother_dstr_sor_ascend(dSTRmat* A, dvector* b, dvector* u, double* diaginv, double weight)  // :981
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, STR_ORDER_ASCEND, nullptr, false, weight, diaginv, false);
+}
+void fasp_smoother_dstr_sor_descend(dSTRmat* A, dvector* b, dvector* u, double* diaginv, double weight)  // :1102
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, STR_ORDER_DESCEND, nullptr, false, weight, diaginv, false);
+}
+void fasp_smoother_dstr_sor_order(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, double weight)  // :1224
+{
+    FASP_ENTRY();
+    if (!mark) { std::fprintf(stderr, "### ERROR: %s: the user-defined order needs a mark array\n", __func__); return; }
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, STR_ORDER_USER, mark, false, weight, diaginv, false);
+}
+void fasp_smoother_dstr_sor_cf(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, const int order, const double weight)  // :1355
+{
+    FASP_ENTRY();
+    str_smoother_public(__func__, A, b, u, STR_SWEEP_SOR, order, mark, true, weight, diaginv, false);
+}
+
+// ---- the dev entries of the sweeps (fasp_hip_dev.h) -------------------------------------------------------------------------------------
+int fasp_hip_str_sweep(const dSTRmat* A, int kind, int order, const int* mark, double weight, const double* diaginv, const double* b, double* u,
+                       int nsweeps, int* info)
+{
+    FASP_ENTRY();
+    if (!A || !b || !u || nsweeps < 0) return ERROR_INPUT_PAR;
+    return str_sweep_run(__func__, A, kind, order, mark, false, weight, diaginv, true, b, u, nsweeps, info, 0, nullptr, nullptr);
+}
+int fasp_hip_str_sweep_form(const dSTRmat* A, int order, const int* mark)
+{
+    FASP_ENTRY();
+    StrSweepPrep P;
+    const int st = str_sweep_prepare(__func__, A, STR_SWEEP_GS, order, mark, false, nullptr, false, false, P);
+    if (st < 0) return st;
+    if (!P.todo) { std::printf("fasp_hip_str_sweep_form: mark is NULL and the order is neither ASCEND nor DESCEND: nothing is swept\n"); return -1; }
+    if (!P.D.geo) std::printf("fasp_hip_str_sweep_form: not the geometric form: %s\n", P.D.why);
+    else if (!P.natural) std::printf("fasp_hip_str_sweep_form: not the geometric form: the order is a sequence or a C/F marking\n");
+    std::fflush(stdout);
+    return P.form;
+}
+int fasp_hip_str_sweep_levels(const dSTRmat* A, int order, const int* mark, int* visit, int* level, int cap)
+{
+    FASP_ENTRY();
+    StrSweepPrep P;
+    const int st = str_sweep_prepare(__func__, A, STR_SWEEP_GS, order, mark, false, nullptr, false, false, P);
+    if (st < 0) return st;
+    if (!P.todo) return 0;
+    if (P.form != STR_SWF_LIST) str_sweep_visits(P.D.ngrid, order, mark, P.cf, false, P.seq);
+    std::vector<int> lev;
+    (void)str_sweep_levels(P.D, P.seq, lev);
+    for (size_t v = 0; v < P.seq.size() && (int)v < cap; ++v) {
+        if (visit) visit[v] = P.seq[v] & 0x7fffffff;
+        if (level) level[v] = lev[v];
+    }
+    return (int)P.seq.size();
+}
+double fasp_hip_time_str_sweep(const dSTRmat* A, int kind, int order, const int* mark, double weight, int reps)
+{
+    FASP_ENTRY();
+    if (!A || reps <= 0 || A->ngrid <= 0 || A->nc < 1 || A->nc > 7) return -1.0;
+    const size_t n = (size_t)A->ngrid * A->nc;
+    std::vector<double> hb(n), hu(n, 0.0);
+    for (size_t i = 0; i < n; ++i) hb[i] = std::sin(0.37 * (double)i) + 0.1;
+    double ms = -1.0;
+    const int st = str_sweep_run(__func__, A, kind, order, mark, false, weight, nullptr, true, hb.data(), hu.data(), 1, nullptr, reps, &ms, nullptr);
+    return st < 0 ? -1.0 : ms;
+}

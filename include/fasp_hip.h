@@ -661,6 +661,37 @@ void fasp_ilu_dstr_setup1(dSTRmat* A, dSTRmat* LU);                 /* BlaILUSet
 void fasp_precond_dstr_ilu0(double* r, double* z, void* data);      /* PreSTR.c:71 */
 void fasp_precond_dstr_ilu1(double* r, double* z, void* data);      /* PreSTR.c:349 */
 int  fasp_solver_dstr_krylov_ilu(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam, ILU_param* iluparam);   /* SolSTR.c:236 */
+/* The structured smoothers (ItrSmootherSTR.c): one sweep on the device, host vectors of ngrid*nc, one-shot
+ * (upload, sweep, download) as fasp_smoother_dcsr_gs, with the reference's result bit for bit.  Orders, as _gs1 / _sor1 dispatch them:
+ * mark == NULL: ASCEND or DESCEND, any other order does nothing; mark != NULL: USERDEFINED -- mark is the visiting sequence of the
+ * ngrid points -- and any other order is the C/F form with FIRST = order, SECOND = -order: the points marked FIRST ascending, then those
+ * marked SECOND; points marked neither are not visited (the _cf entries take this form whatever `order` is).  The entries without the
+ * trailing 1 invert the diagonal blocks on the host for nc > 1 (fasp_smat_inv); the others take them as diaginv (NULL for nc = 1).
+ * The reference's scalar fasp_smoother_dstr_sor_cf closes the points of its SECOND pass without the weight (ItrSmootherSTR.c:1443); so
+ * does this one.  nc < 1: the reference's message, nothing done.  Refused with a message, u untouched: a USERDEFINED sequence with an
+ * entry outside 0 .. ngrid-1 or a point named twice; NULL diaginv with nc > 1 where it is an argument.  nc > 7 and any matrix
+ * fasp_hip_str_form refuses end the process like the other STR entries. */
+#ifndef ASCEND
+#define ASCEND      12   /* fasp_const.h: the orders of the structured smoothers */
+#define DESCEND     21
+#define USERDEFINED 0
+#define CPFIRST     1
+#define FPFIRST     (-1)
+#endif
+void fasp_smoother_dstr_jacobi(dSTRmat* A, dvector* b, dvector* u);                                                   /* ItrSmootherSTR.c:43 */
+void fasp_smoother_dstr_jacobi1(dSTRmat* A, dvector* b, dvector* u, double* diaginv);                                 /* ItrSmootherSTR.c:92 */
+void fasp_smoother_dstr_gs(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark);                           /* ItrSmootherSTR.c:217 */
+void fasp_smoother_dstr_gs1(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, double* diaginv);         /* ItrSmootherSTR.c:277 */
+void fasp_smoother_dstr_gs_ascend(dSTRmat* A, dvector* b, dvector* u, double* diaginv);                               /* ItrSmootherSTR.c:322 */
+void fasp_smoother_dstr_gs_descend(dSTRmat* A, dvector* b, dvector* u, double* diaginv);                              /* ItrSmootherSTR.c:438 */
+void fasp_smoother_dstr_gs_order(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark);                     /* ItrSmootherSTR.c:556 */
+void fasp_smoother_dstr_gs_cf(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, const int order);       /* ItrSmootherSTR.c:680 */
+void fasp_smoother_dstr_sor(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, const double weight);     /* ItrSmootherSTR.c:873 */
+void fasp_smoother_dstr_sor1(dSTRmat* A, dvector* b, dvector* u, const int order, int* mark, double* diaginv, const double weight);   /* ItrSmootherSTR.c:935 */
+void fasp_smoother_dstr_sor_ascend(dSTRmat* A, dvector* b, dvector* u, double* diaginv, double weight);               /* ItrSmootherSTR.c:981 */
+void fasp_smoother_dstr_sor_descend(dSTRmat* A, dvector* b, dvector* u, double* diaginv, double weight);              /* ItrSmootherSTR.c:1102 */
+void fasp_smoother_dstr_sor_order(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, double weight);     /* ItrSmootherSTR.c:1224 */
+void fasp_smoother_dstr_sor_cf(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, const int order, const double weight);   /* ItrSmootherSTR.c:1355 */
 
 /* Matrix-free interface (SolMatFree.c:58/:157/:201; KryPcg.c:1260, KryPbcgs.c:1349, KryPgcg.c:213,
  * KryPgmres.c:1309, KryPvgmres.c:1468, KryPvfgmres.c:1026, KryPminres.c:1283 -- the reference keeps older texts of

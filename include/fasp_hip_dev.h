@@ -230,6 +230,26 @@ double fasp_hip_time_str_mxv(const dSTRmat* A, int reps);
 int    fasp_hip_str_ilu_form(const dSTRmat* LU, int lfil);
 int    fasp_hip_str_ilu_apply(const dSTRmat* LU, int lfil, const double* r, double* z);
 double fasp_hip_time_str_ilu(const dSTRmat* LU, int lfil, int reps);
+/* The structured smoothers on a resident copy (csrc/str_sweep.hip.h).  kind: 0 Jacobi, 1 Gauss-Seidel, 2 SOR;
+ * (order, mark) as fasp_smoother_dstr_gs1 takes them (Jacobi ignores both); diaginv: the inverted diagonal blocks for nc > 1, NULL: inverted
+ * on the host as the public entries without the trailing 1 do.
+ * fasp_hip_str_sweep: matrix, plan and vectors uploaded once, nsweeps sweeps, u back.  info (8 ints, may be NULL): {form that ran -- 0 one
+ * launch per level x + y + z, 1 planes pipelined over workgroups, 2 the ordered form (level list), 3 Jacobi --, launches of a sweep, levels,
+ * workgroups of the largest launch, visits of a sweep, 1 when the matrix is grid-like, 0, 0}.  ERROR_INPUT_PAR, u untouched: a matrix the
+ * library refuses (nc outside 1 .. 7, ...), kind outside 0 .. 2, a USERDEFINED sequence that is not a permutation of the grid points;
+ * ERROR_MISC: no device, or a poll of the pipelined form that ran out (and the report of seq_err_check; later calls take the level form).
+ * fasp_hip_str_sweep_form (pure host code): the form str_sweep_plan chooses under the tune keys in force, and on stdout why it is not a
+ * geometric one; -1 when nothing would be swept (mark NULL, order neither ASCEND nor DESCEND), ERROR_INPUT_PAR as above.
+ * fasp_hip_str_sweep_levels (pure host code): the visits of the sweep in the reference's order and the level the ordered form gives each
+ * (visit, level: `cap` ints each, either may be NULL); returns the number of visits.
+ * fasp_hip_time_str_sweep: mean milliseconds per sweep over `reps` sweeps after one warm-up sweep (HIP events); -1: no device or refused.
+ * Tune keys: str_sweep_form (-1 default: by str_sweep_plan; 0 / 1 / 2 force a form where it applies), str_sweep_wgs (workgroups of the
+ * pipelined form at most; 0: default). */
+int    fasp_hip_str_sweep(const dSTRmat* A, int kind, int order, const int* mark, double weight, const double* diaginv, const double* b,
+                          double* u, int nsweeps, int* info);
+int    fasp_hip_str_sweep_form(const dSTRmat* A, int order, const int* mark);
+int    fasp_hip_str_sweep_levels(const dSTRmat* A, int order, const int* mark, int* visit, int* level, int cap);
+double fasp_hip_time_str_sweep(const dSTRmat* A, int kind, int order, const int* mark, double weight, int reps);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
