@@ -70,6 +70,8 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_smoother_dstr_sor", "fasp_smoother_dstr_sor1", "fasp_smoother_dstr_sor_ascend", "fasp_smoother_dstr_sor_descend",
     "fasp_smoother_dstr_sor_order", "fasp_smoother_dstr_sor_cf",
     "fasp_hip_str_sweep", "fasp_hip_str_sweep_form", "fasp_hip_str_sweep_levels", "fasp_hip_time_str_sweep",
+    "fasp_generate_diaginv_block", "fasp_smoother_dstr_swz", "fasp_precond_dstr_blockgs", "fasp_solver_dstr_krylov_blockgs",
+    "fasp_hip_str_swz", "fasp_hip_str_swz_levels", "fasp_hip_time_str_swz",
 ]
 
 
@@ -338,6 +340,18 @@ def lib():
     L.fasp_hip_str_sweep_levels.argtypes = [A_, C.c_int, I_, I_, I_, C.c_int]
     L.fasp_hip_time_str_sweep.argtypes = [A_, C.c_int, C.c_int, I_, C.c_double, C.c_int]
     L.fasp_hip_time_str_sweep.restype = C.c_double
+    # the structured block Gauss-Seidel (Schwarz) smoother and preconditioner (ItrSmootherSTR.c:1543 / :1665, PreSTR.c:1715, SolSTR.c:323)
+    IV_ = P(T.ivector)
+    L.fasp_generate_diaginv_block.argtypes = [A_, IV_, V_, IV_]
+    L.fasp_generate_diaginv_block.restype = None
+    L.fasp_smoother_dstr_swz.argtypes = [A_, V_, V_, V_, IV_, IV_, IV_]
+    L.fasp_smoother_dstr_swz.restype = None
+    L.fasp_precond_dstr_blockgs.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_dstr_blockgs.restype = None
+    L.fasp_solver_dstr_krylov_blockgs.argtypes = [A_, V_, V_, P(T.ITS_param), IV_, IV_]
+    L.fasp_hip_str_swz.argtypes = [A_, I_, C.c_int, I_, D_, D_, C.c_int, I_]
+    L.fasp_hip_str_swz_levels.argtypes = [A_, I_, C.c_int, I_, I_, I_, C.c_int]
+    L.fasp_hip_time_str_swz.argtypes = [A_, I_, C.c_int, I_, C.c_int, D_, D_, I_]
     return L
 
 

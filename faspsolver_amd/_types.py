@@ -79,6 +79,17 @@ class ivector(C.Structure):
     _fields_ = [("row", C.c_int), ("val", c_int_p)]
 
 
+class precond_data_str(C.Structure):
+    """fasp.h:984: data of the preconditioners of a dSTRmat; fasp_precond_dstr_blockgs reads A_str, diaginv, pivot, order and neigh."""
+    _fields_ = [("AMG_type", C.c_short), ("print_level", C.c_short), ("maxit", C.c_int), ("max_levels", C.c_short), ("tol", C.c_double),
+                ("cycle_type", C.c_short), ("smoother", C.c_short), ("presmooth_iter", C.c_short), ("postsmooth_iter", C.c_short),
+                ("coarsening_type", C.c_short), ("relaxation", C.c_double), ("coarse_scaling", C.c_short), ("mgl_data", C.c_void_p),
+                ("LU", C.c_void_p), ("scaled", C.c_short), ("A", C.c_void_p), ("A_str", C.POINTER(dSTRmat)), ("SS_str", C.POINTER(dSTRmat)),
+                ("diaginv", C.POINTER(dvector)), ("pivot", C.POINTER(ivector)), ("diaginvS", C.POINTER(dvector)),
+                ("pivotS", C.POINTER(ivector)), ("order", C.POINTER(ivector)), ("neigh", C.POINTER(ivector)), ("r", dvector),
+                ("w", c_double_p)]
+
+
 class ITS_param(C.Structure):
     _fields_ = [("print_level", C.c_short), ("itsolver_type", C.c_short),
                 ("decoup_type", C.c_short), ("precond_type", C.c_short),

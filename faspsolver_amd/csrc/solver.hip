@@ -168,6 +168,7 @@ static inline int vec_grid(int n)
 #include "str.hip.h"
 #include "str_ilu.hip.h"
 #include "str_sweep.hip.h"
+#include "str_swz.hip.h"
 
 // ===========================================================================
 // C ABI
@@ -1239,6 +1240,7 @@ struct PcState {
     IluDev*           ilu = nullptr;
     std::unique_ptr<IluDev, void (*)(IluDev*)> ilu_tmp{nullptr, ilu_dev_destroy};
     std::unique_ptr<StrIluDev> strilu;   // structured ILU factor, uploaded for this solve
+    std::unique_ptr<StrSwzDev> strswz;   // structured block Gauss-Seidel: the caller's factors, uploaded for this solve
     std::unique_ptr<TmpVec> ddiag, dz;   // device diagonal; output of the diagonal and of a foreign preconditioner
     std::vector<double> hr, hz;          // host staging of a foreign preconditioner
     double* out(int n) { if (!dz) dz.reset(new TmpVec(nullptr, (size_t)n)); return dz->d; }
@@ -1322,10 +1324,31 @@ bool bind_ilu_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
     K.pc = [M](double* in, double** out) { *out = M->z; return str_ilu_apply(*M, in, M->z); };
     return true;
 }
+// the reference's block Gauss-Seidel preconditioner (PreSTR.c:1715): recognised by its address.  Factors that live on the device already
+// (fasp_solver_dstr_krylov_blockgs) are found through the address of the data; a caller's host factors are checked, repacked and uploaded once
+// per solve.  Per application: z = 0 and one sweep, no host traffic.  Data the sweep refuses ends the solve (ERROR_INPUT_PAR), as the
+// direct call would leave z untouched; data for another matrix size leaves it a foreign host function.
+bool bind_blockgs_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
+{
+    if (!(pc && pc->data && pc->fct == fasp_precond_dstr_blockgs)) return false;
+    const precond_data_str* d = static_cast<const precond_data_str*>(pc->data);
+    if (!d->A_str || d->A_str->nc != nc || (long long)d->A_str->ngrid * nc != n) return false;
+    StrSwzDev* M = str_swz_resident(pc->data);
+    if (!M) {
+        StrSwzPlan P;
+        if (str_swz_plan("fasp_precond_dstr_blockgs", d->A_str, d->neigh, d->order, true, P) < 0 ||
+            str_swz_check_factors("fasp_precond_dstr_blockgs", P, d->diaginv, d->pivot) < 0) { *st = ERROR_INPUT_PAR; return true; }
+        S.strswz.reset(new StrSwzDev(d->A_str, std::move(P), d->diaginv, d->pivot));
+        if (!S.strswz->ok) { *st = S.strswz->st; return true; }
+        M = S.strswz.get();
+    }
+    K.pc = [M](double* in, double** out) { *out = M->u; return M->precond(in, M->u); };
+    return true;
+}
 // the structured family's device preconditioners: its ILU factors (a format of their own: no IluDev) and the block diagonal
 bool bind_pc_str(precond* pc, int n, int nc, PcState& S, KOps& K, int* st)
 {
-    return bind_ilu_str(pc, n, nc, S, K, st) || bind_diag_str(pc, n, nc, S, K, st);
+    return bind_ilu_str(pc, n, nc, S, K, st) || bind_blockgs_str(pc, n, nc, S, K, st) || bind_diag_str(pc, n, nc, S, K, st);
 }
 // the structured family knows no device AMG handle and no MSR factor (its ILU is bound by bind_ilu_str)
 int find_amg_none(precond*, int, PcState&) { return FASP_SUCCESS; }

@@ -567,3 +567,240 @@ double fasp_hip_time_str_sweep(const dSTRmat* A, int kind, int order, const int*
     const int st = str_sweep_run(__func__, A, kind, order, mark, false, weight, nullptr, true, hb.data(), hu.data(), 1, nullptr, reps, &ms, nullptr);
     return st < 0 ? -1.0 : ms;
 }
+
+// ---- block Gauss-Seidel (Schwarz): ItrSmootherSTR.c:1543 / :1665, PreSTR.c:1715, SolSTR.c:323 (csrc/str_swz.hip.h) ----
+namespace {
+// what every entry checks first.  0: go on; 1: nothing to do, said (nc < 1: the reference's message); a matrix the library refuses ends the process
+int str_swz_gate(const char* fn, const dSTRmat* A)
+{
+    if (!A) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", fn); return 1; }
+    if (A->nc < 1) { std::printf("### ERROR: nc is illegal! [%s]\n", fn); std::fflush(stdout); return 1; }
+    if (str_plan(A, nullptr) < 0) die_str(fn, ERROR_INPUT_PAR);
+    return 0;
+}
+void str_swz_fail(const char* fn, int st)
+{
+    if (st == ERROR_MISC && !g_ctx.ready) die_str(fn, 0);
+    std::fprintf(stderr, "### ERROR: %s: failed (%d)\n", fn, st);
+    std::exit(st);
+}
+int str_swz_refuse_stopped(const char* fn, const StrSwzDev& M)
+{
+    if (!M.nstopped) return FASP_SUCCESS;
+    std::fprintf(stderr, "### ERROR: %s: the factorisation of %d patch(es) stopped at a pivot below 1e-20\n", fn, M.nstopped);
+    return ERROR_INPUT_PAR;
+}
+// one sweep (zero_u: from u = 0) with the resident object M on host vectors
+int str_swz_oneshot(StrSwzDev& M, const double* b, double* u, bool zero_u)
+{
+    const size_t n = (size_t)M.P.ngrid * M.P.nc;
+    HIPCK(hipMemcpyAsync(M.b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+    if (zero_u) HIPCK(hipMemsetAsync(M.u, 0, sizeof(double) * n, g_ctx.stream));
+    else HIPCK(hipMemcpyAsync(M.u, u, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+    const int st = M.sweep(M.b, M.u);
+    HIPCK(hipStreamSynchronize(g_ctx.stream));
+    if (st < 0) return st;
+    HIPCK(hipMemcpy(u, M.u, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return FASP_SUCCESS;
+}
+void str_swz_info(const StrSwzDev& M, int* info)
+{
+    if (!info) return;
+    info[0] = M.P.levels; info[1] = M.launches; info[2] = (int)M.P.seq.size(); info[3] = M.P.widest; info[4] = M.P.ms; info[5] = M.nswap;
+    info[6] = M.nstopped; info[7] = 0;
+}
+}  // namespace
+
+void fasp_generate_diaginv_block(dSTRmat* A, ivector* neigh, dvector* diaginv, ivector* pivot)  // ItrSmootherSTR.c:1543
+{
+    FASP_ENTRY();
+    if (str_swz_gate(__func__, A)) return;
+    if (!diaginv || !pivot) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", __func__); return; }
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, neigh, nullptr, false, P) < 0) return;   // said; diaginv and pivot untouched
+    const int ngrid = P.ngrid, nc = P.nc;
+    const size_t w = ((size_t)P.nneigh + 1) * nc, nd = w * w * (size_t)ngrid, np = w * (size_t)ngrid;
+    if (nd > 0xffffffffull) { std::fprintf(stderr, "### ERROR: %s: the factors do not fit one fasp_mem_calloc block\n", __func__); return; }
+    if (ctx_init() < 0) die_str(__func__, 0);
+    const std::vector<int> msize = P.msize;
+    const int ms = P.ms;
+    StrSwzDev M(A, std::move(P), nullptr, nullptr);
+    if (!M.ok) str_swz_fail(__func__, M.st);
+    std::vector<double> hf(std::max<size_t>(M.nfac, 1));
+    std::vector<int> hp(std::max<size_t>(M.npiv, 1));
+    if ((M.nfac && hipMemcpy(hf.data(), M.fac, sizeof(double) * M.nfac, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (M.npiv && hipMemcpy(hp.data(), M.piv, sizeof(int) * M.npiv, hipMemcpyDeviceToHost) != hipSuccess)) str_swz_fail(__func__, ERROR_MISC);
+    double* temp = (double*)fasp_mem_calloc((unsigned)nd, sizeof(double));
+    int*    tmp = (int*)fasp_mem_calloc((unsigned)np, sizeof(int));
+    size_t mem_inv = 0, mem_pivot = 0;
+    const size_t ms2 = (size_t)ms * ms;
+    for (int i = 0; i < ngrid; ++i) {   // (the list of a factorisation-only plan is the natural order: slot i is point i)
+        const int m = msize[(size_t)i];
+        const size_t s = (size_t)i, fb = (s >> 6) * ms2 * 64 + (s & 63), pb = (s >> 6) * (size_t)ms * 64 + (s & 63);
+        diaginv[i].row = m * m; diaginv[i].val = temp + mem_inv;
+        pivot[i].row = m; pivot[i].val = tmp + mem_pivot;
+        for (int e = 0; e < m * m; ++e) diaginv[i].val[e] = hf[fb + (size_t)e * 64];
+        for (int k = 0; k < m; ++k) pivot[i].val[k] = hp[pb + (size_t)k * 64];
+        mem_inv += (size_t)m * m; mem_pivot += (size_t)m;
+    }
+}
+
+void fasp_smoother_dstr_swz(dSTRmat* A, dvector* b, dvector* u, dvector* diaginv, ivector* pivot, ivector* neigh, ivector* order)  // ItrSmootherSTR.c:1665
+{
+    FASP_ENTRY();
+    if (str_swz_gate(__func__, A)) return;
+    if (!b || !u || !b->val || !u->val) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", __func__); return; }
+    const long long n = (long long)A->ngrid * A->nc;
+    if (A->ngrid > 0 && (b->row < n || u->row < n)) { std::fprintf(stderr, "### ERROR: %s: b and u need ngrid * nc = %lld entries\n", __func__, n); return; }
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, neigh, order, true, P) < 0 || str_swz_check_factors(__func__, P, diaginv, pivot) < 0) return;   // said, u untouched
+    if (P.ngrid == 0) return;
+    if (ctx_init() < 0) die_str(__func__, 0);
+    StrSwzDev M(A, std::move(P), diaginv, pivot);
+    if (!M.ok) str_swz_fail(__func__, M.st);
+    const int st = str_swz_oneshot(M, b->val, u->val, false);
+    if (st < 0) str_swz_fail(__func__, st);
+}
+
+void fasp_precond_dstr_blockgs(double* r, double* z, void* data)  // PreSTR.c:1715
+{
+    FASP_ENTRY();
+    const precond_data_str* d = static_cast<const precond_data_str*>(data);
+    if (!r || !z || !d) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", __func__); return; }
+    if (str_swz_gate(__func__, d->A_str)) return;
+    if (d->A_str->ngrid == 0) return;
+    if (StrSwzDev* R = str_swz_resident(data)) {   // factors that live on the device (fasp_solver_dstr_krylov_blockgs)
+        const int st = str_swz_oneshot(*R, r, z, true);
+        if (st < 0) str_swz_fail(__func__, st);
+        return;
+    }
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, d->A_str, d->neigh, d->order, true, P) < 0 || str_swz_check_factors(__func__, P, d->diaginv, d->pivot) < 0) return;   // said, z untouched
+    if (ctx_init() < 0) die_str(__func__, 0);
+    StrSwzDev M(d->A_str, std::move(P), d->diaginv, d->pivot);
+    if (!M.ok) str_swz_fail(__func__, M.st);
+    const int st = str_swz_oneshot(M, r, z, true);
+    if (st < 0) str_swz_fail(__func__, st);
+}
+
+// SolSTR.c:323: every patch factored on the device (the factors stay there), then the Krylov method with the sweep bound (bind_blockgs_str)
+int fasp_solver_dstr_krylov_blockgs(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam, ivector* neigh, ivector* order)
+{
+    FASP_ENTRY();
+    if (!itparam || !A || !b || !x) return ERROR_INPUT_PAR;
+    const short prtlvl = itparam->print_level;
+    if (A->nc < 1) { std::printf("### ERROR: nc is illegal! [%s]\n", __func__); std::fflush(stdout); return ERROR_INPUT_PAR; }
+    if (str_plan(A, nullptr) < 0) return ERROR_INPUT_PAR;
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, neigh, order, true, P) < 0) return ERROR_INPUT_PAR;
+    if (ctx_init() < 0) die_no_device(__func__);
+    const double t0 = wall_seconds();
+    StrSwzDev M(A, std::move(P), nullptr, nullptr);
+    if (!M.ok) return M.st;
+    if (str_swz_refuse_stopped(__func__, M) < 0) return ERROR_INPUT_PAR;
+    precond_data_str pcdata{};
+    pcdata.A_str = A; pcdata.order = order; pcdata.neigh = neigh;   // diaginv, pivot: NULL -- the factors are M's
+    precond pc{&pcdata, fasp_precond_dstr_blockgs};
+    const double setup_time = wall_seconds() - t0;
+    if (prtlvl > PRINT_NONE) std::printf("Preconditioner setup costs %f seconds.\n", setup_time);
+    const double t1 = wall_seconds();
+    g_swz_resident.emplace_back(&pcdata, &M);
+    const int status = fasp_solver_dstr_itsolver(A, b, x, &pc, itparam);
+    g_swz_resident.pop_back();
+    if (prtlvl >= PRINT_MIN) {
+        const double solve_time = wall_seconds() - t1;
+        std::printf("Iterative solver costs %.4f seconds\n", solve_time);
+        std::printf("BlockGS_Krylov method totally costs %.4f seconds\n", setup_time + solve_time);
+    }
+    return status;
+}
+
+// ---- the dev entries of the block Gauss-Seidel sweep (fasp_hip_dev.h) --------------------------------------------------------------------
+namespace {
+struct StrSwzRaw {   // (neigh, nneigh, order) of a dev entry as the ivectors the plan takes
+    ivector nv{0, nullptr}, ov{0, nullptr};
+    StrSwzRaw(const dSTRmat* A, const int* neigh, int nneigh, const int* order)
+    {
+        const long long ngrid = A ? A->ngrid : 0;
+        if (neigh && nneigh > 0 && ngrid * nneigh <= 0x7fffffffLL) { nv.row = (int)(ngrid * nneigh); nv.val = const_cast<int*>(neigh); }
+        if (order) { ov.row = (int)ngrid; ov.val = const_cast<int*>(order); }
+    }
+    const ivector* n() const { return nv.val ? &nv : nullptr; }
+    const ivector* o() const { return ov.val ? &ov : nullptr; }
+};
+}  // namespace
+
+int fasp_hip_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, const double* b, double* u, int nsweeps, int* info)
+{
+    FASP_ENTRY();
+    if (info) std::fill(info, info + 8, 0);
+    if (!A || !b || !u || nsweeps < 0 || nneigh < 0) return ERROR_INPUT_PAR;
+    const StrSwzRaw raw(A, neigh, nneigh, order);
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, raw.n(), raw.o(), true, P) < 0) return ERROR_INPUT_PAR;
+    if (P.ngrid == 0) return FASP_SUCCESS;
+    if (ctx_init() < 0) return ERROR_MISC;
+    StrSwzDev M(A, std::move(P), nullptr, nullptr);
+    if (!M.ok) return M.st;
+    str_swz_info(M, info);
+    if (str_swz_refuse_stopped(__func__, M) < 0) return ERROR_INPUT_PAR;
+    const size_t n = (size_t)M.P.ngrid * M.P.nc;
+    HIPCK(hipMemcpy(M.b, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(M.u, u, sizeof(double) * n, hipMemcpyHostToDevice));
+    int st = FASP_SUCCESS;
+    for (int s = 0; s < nsweeps && st >= 0; ++s) st = M.sweep(M.b, M.u);
+    HIPCK(hipStreamSynchronize(g_ctx.stream));
+    if (st < 0) return st;
+    HIPCK(hipMemcpy(u, M.u, sizeof(double) * n, hipMemcpyDeviceToHost));
+    str_swz_info(M, info);
+    return FASP_SUCCESS;
+}
+int fasp_hip_str_swz_levels(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int* visit, int* level, int cap)
+{
+    FASP_ENTRY();
+    if (!A || nneigh < 0) return ERROR_INPUT_PAR;
+    const StrSwzRaw raw(A, neigh, nneigh, order);
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, raw.n(), raw.o(), true, P) < 0) return ERROR_INPUT_PAR;
+    for (size_t v = 0; v < P.seq.size() && (int)v < cap; ++v) {
+        if (visit) visit[v] = P.seq[v];
+        if (level) level[v] = P.lev[v];
+    }
+    return (int)P.seq.size();
+}
+int fasp_hip_time_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int reps, double* ms_factor, double* ms_sweep, int* info)
+{
+    FASP_ENTRY();
+    if (info) std::fill(info, info + 8, 0);
+    if (!A || reps <= 0 || nneigh < 0 || A->ngrid <= 0) return ERROR_INPUT_PAR;
+    const StrSwzRaw raw(A, neigh, nneigh, order);
+    StrSwzPlan P;
+    if (str_swz_plan(__func__, A, raw.n(), raw.o(), true, P) < 0) return ERROR_INPUT_PAR;
+    if (ctx_init() < 0) return ERROR_MISC;
+    StrSwzDev M(A, std::move(P), nullptr, nullptr);   // (the warm-up factorisation)
+    if (!M.ok) return M.st;
+    str_swz_info(M, info);
+    if (str_swz_refuse_stopped(__func__, M) < 0) return ERROR_INPUT_PAR;
+    const size_t n = (size_t)M.P.ngrid * M.P.nc;
+    std::vector<double> hb(n);
+    for (size_t i = 0; i < n; ++i) hb[i] = std::sin(0.37 * (double)i) + 0.1;
+    HIPCK(hipMemcpy(M.b, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1, e2, e3;
+    HIPCK(hipEventCreate(&e0)); HIPCK(hipEventCreate(&e1)); HIPCK(hipEventCreate(&e2)); HIPCK(hipEventCreate(&e3));
+    int st = FASP_SUCCESS;
+    HIPCK(hipEventRecord(e0, g_ctx.stream));
+    for (int i = 0; i < reps && st >= 0; ++i) st = M.launch_factor();
+    HIPCK(hipEventRecord(e1, g_ctx.stream));
+    if (st >= 0) st = M.precond(M.b, M.u);   // warm-up
+    HIPCK(hipEventRecord(e2, g_ctx.stream));
+    for (int i = 0; i < reps && st >= 0; ++i) st = M.precond(M.b, M.u);
+    HIPCK(hipEventRecord(e3, g_ctx.stream));
+    HIPCK(hipEventSynchronize(e3));
+    float tf = 0.f, ts = 0.f;
+    (void)hipEventElapsedTime(&tf, e0, e1); (void)hipEventElapsedTime(&ts, e2, e3);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
+    str_swz_info(M, info);
+    if (ms_factor) *ms_factor = (double)tf / reps;
+    if (ms_sweep) *ms_sweep = (double)ts / reps;
+    return st;
+}

@@ -360,6 +360,31 @@ typedef struct {
     dvector diag;   /* ngrid inverse diagonal blocks of nc*nc doubles */
 } precond_diag_str;
 
+/* fasp.h:984  data of the preconditioners of a dSTRmat (the reference's CPR-type preconditioners); fasp_precond_dstr_blockgs reads
+ * A_str, diaginv, pivot, order and neigh, the other members are carried for layout only */
+typedef struct {
+    short     AMG_type, print_level;
+    int       maxit;
+    short     max_levels;
+    double    tol;
+    short     cycle_type, smoother, presmooth_iter, postsmooth_iter, coarsening_type;
+    double    relaxation;
+    short     coarse_scaling;
+    AMG_data* mgl_data;
+    ILU_data* LU;
+    short     scaled;
+    dCSRmat*  A;
+    dSTRmat  *A_str, *SS_str;
+    dvector*  diaginv;    /* ngrid factored patches (fasp_generate_diaginv_block) */
+    ivector*  pivot;      /* ... and their pivots */
+    dvector*  diaginvS;
+    ivector*  pivotS;
+    ivector*  order;      /* the visiting sequence, NULL: natural */
+    ivector*  neigh;      /* ngrid * nneigh neighbours, < 0: absent; NULL: none */
+    dvector   r;
+    double*   w;
+} precond_data_str;
+
 /* fasp.h:1109  matrix-free operator: y = A x through a function pointer */
 typedef struct {
     void* data;
@@ -692,6 +717,27 @@ void fasp_smoother_dstr_sor_ascend(dSTRmat* A, dvector* b, dvector* u, double* d
 void fasp_smoother_dstr_sor_descend(dSTRmat* A, dvector* b, dvector* u, double* diaginv, double weight);              /* ItrSmootherSTR.c:1102 */
 void fasp_smoother_dstr_sor_order(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, double weight);     /* ItrSmootherSTR.c:1224 */
 void fasp_smoother_dstr_sor_cf(dSTRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, const int order, const double weight);   /* ItrSmootherSTR.c:1355 */
+
+/* The block Gauss-Seidel (Schwarz) smoother and preconditioner of a structured matrix.  The patch of grid point i is
+ * [i, neigh[i * nneigh + 0 .. nneigh)] without the absent entries (< 0; nneigh = neigh->row / ngrid, neigh == NULL: none), m = members * nc
+ * rows; a point may be named twice or name itself.  order: the visiting sequence (ngrid entries, a point may come twice), NULL: natural.
+ * fasp_generate_diaginv_block assembles and factors every patch on the device (LU with row interchanges, fasp_smat_lu_decomp) and delivers
+ * the reference's host layout and bytes: diaginv[i].row = m_i^2, pivot[i].row = m_i, all values carved in order from one zero-initialised
+ * fasp_mem_calloc block of ((nneigh+1) nc)^2 ngrid doubles / (nneigh+1) nc ngrid ints (diaginv[0].val and pivot[0].val are the bases); a patch
+ * whose factorisation stops (a pivot below 1e-20) holds what the reference leaves.  fasp_smoother_dstr_swz: one sweep, one-shot (upload, the
+ * caller's factors repacked, sweep, download), the reference's result bit for bit.  fasp_precond_dstr_blockgs (data: precond_data_str*):
+ * z = 0 and one sweep with b = r; handed to an STR Krylov method it is recognised by its address and stays on the device, called directly
+ * (also from inside another preconditioner of a running solve) it is one-shot.  fasp_solver_dstr_krylov_blockgs factors on the device (the
+ * factors are never downloaded), solves with fasp_solver_dstr_itsolver and prints the reference's lines.
+ * nc < 1: the reference's message, nothing done.  nc > 7 and any matrix fasp_hip_str_form refuses end the process like the other STR entries
+ * (the solver entry returns ERROR_INPUT_PAR).  Refused with a message, u / z untouched (the solver entry: ERROR_INPUT_PAR): a neigh entry >=
+ * ngrid, neigh->row no multiple of ngrid, an order of fewer than ngrid entries or with an entry outside 0 .. ngrid-1, a patch of more than
+ * 64 rows, factors whose row fields or pivots (k <= pivot[k] < m) do not fit the patches, a factorisation that stopped or a factor with 0.0 on
+ * U's diagonal (the reference would go on with the correction of the visit before).  A factor store that does not fit: ERROR_ALLOC_MEM. */
+void fasp_generate_diaginv_block(dSTRmat* A, ivector* neigh, dvector* diaginv, ivector* pivot);                                          /* ItrSmootherSTR.c:1543 */
+void fasp_smoother_dstr_swz(dSTRmat* A, dvector* b, dvector* u, dvector* diaginv, ivector* pivot, ivector* neigh, ivector* order);      /* ItrSmootherSTR.c:1665 */
+void fasp_precond_dstr_blockgs(double* r, double* z, void* data);                                                                       /* PreSTR.c:1715 */
+int  fasp_solver_dstr_krylov_blockgs(dSTRmat* A, dvector* b, dvector* x, ITS_param* itparam, ivector* neigh, ivector* order);           /* SolSTR.c:323 */
 
 /* Matrix-free interface (SolMatFree.c:58/:157/:201; KryPcg.c:1260, KryPbcgs.c:1349, KryPgcg.c:213,
  * KryPgmres.c:1309, KryPvgmres.c:1468, KryPvfgmres.c:1026, KryPminres.c:1283 -- the reference keeps older texts of

@@ -250,6 +250,19 @@ int    fasp_hip_str_sweep(const dSTRmat* A, int kind, int order, const int* mark
 int    fasp_hip_str_sweep_form(const dSTRmat* A, int order, const int* mark);
 int    fasp_hip_str_sweep_levels(const dSTRmat* A, int order, const int* mark, int* visit, int* level, int cap);
 double fasp_hip_time_str_sweep(const dSTRmat* A, int kind, int order, const int* mark, double weight, int reps);
+/* The block Gauss-Seidel (Schwarz) smoother on a resident copy (csrc/str_swz.hip.h).  neigh: ngrid * nneigh ints (< 0:
+ * absent; NULL or nneigh 0: none), order: ngrid ints or NULL (natural).
+ * fasp_hip_str_swz: matrix, neigh and visit list uploaded once, every patch factored on the device, nsweeps sweeps, u back.  info (8 ints, may
+ * be NULL): {levels, launches of a sweep, visits, visits of the widest level, the largest m, patches with a row interchange, patches whose
+ * factorisation stopped, 0}.  ERROR_INPUT_PAR, u untouched: what the public entries refuse (fasp_hip.h), a stopped patch included (info is
+ * filled all the same); ERROR_ALLOC_MEM: the factor store does not fit; ERROR_MISC: no device.
+ * fasp_hip_str_swz_levels (pure host code): the visits in the reference's order and the level of each (`cap` ints each, either may be NULL);
+ * returns the number of visits.
+ * fasp_hip_time_str_swz: milliseconds (HIP events) of one factorisation (*ms_factor, mean over `reps` after one warm-up) and per sweep
+ * (*ms_sweep, likewise) on a resident copy, info as above; negative: refused or no device. */
+int  fasp_hip_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, const double* b, double* u, int nsweeps, int* info);
+int  fasp_hip_str_swz_levels(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int* visit, int* level, int cap);
+int  fasp_hip_time_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int reps, double* ms_factor, double* ms_sweep, int* info);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
