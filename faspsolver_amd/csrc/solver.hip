@@ -35,6 +35,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "fasp_comm.h"
@@ -165,6 +166,7 @@ static inline int vec_grid(int n)
 }  // namespace fasp
 
 #include "bsr.hip.h"
+#include "str_common.hip.h"
 #include "str.hip.h"
 #include "str_ilu.hip.h"
 #include "str_sweep.hip.h"

@@ -12,18 +12,16 @@
 // and the reference's row segments do not overlap (ngrid >= 2 nxy, resp. 2 nline); the walk is then by ascending offset,
 // the diagonal between -1 and +1.  A band term exists for row i iff 0 <= i + offset < ngrid.
 //
-// Device layout: the walked bands (the diagonal is one of them) one after the other, each `stride` doubles long, every band
-// shifted so that the block of grid point i sits at i * nc * nc whatever the offset (the reference indexes a lower band by
-// its column); the slots without a term hold zeros and are never used.  Lane = scalar row r = i * nc + p: the nc values of
-// block row p are the nc doubles at r * nc, so a wave's loads of a band cover 64 * nc * 8 contiguous bytes; x is read as the
-// contiguous run x[(i + offset) * nc ...], y is read and written once.  No column indices, no atomics, no pass per band.
+// Device layout: the walked bands (the diagonal is one of them) in a StrBands store (str_common.hip.h).  Lane = scalar row r = i * nc + p:
+// the nc values of block row p are the nc doubles at r * nc, so a wave's loads of a band cover 64 * nc * 8 contiguous bytes; x is read as
+// the contiguous run x[(i + offset) * nc ...], y is read and written once.  No column indices, no atomics, no pass per band.
 
 namespace fasp_str {
 
 enum StrForm : int { STR_S = 0, STR_B = 1, STR_N = 2, STR_G = 3 };
 
-// Which form the product of A takes, and the walk: walk[k] = 0 for the diagonal, b + 1 for offdiag[b]; bands that have no
-// term at all (|offset| >= ngrid) are left out.  Negative: a matrix the library refuses (ERROR_INPUT_PAR).  Pure host code.
+// Which form the product of A takes, and the walk: walk[k] = -1 for the diagonal, b for offdiag[b] (as str_block names them);
+// bands that have no term at all (|offset| >= ngrid) are left out.  Negative: a matrix the library refuses (ERROR_INPUT_PAR).  Pure host code.
 static int str_plan(const dSTRmat* A, std::vector<int>* walk)
 {
     if (!A || A->nc < 1 || A->nc > 7 || A->nband < 0 || A->ngrid < 0) return ERROR_INPUT_PAR;
@@ -52,14 +50,14 @@ static int str_plan(const dSTRmat* A, std::vector<int>* walk)
         walk->clear();
         if (canonical) {   // ascending offsets, the diagonal in the middle; every band has terms (ngrid >= 2 |offset|)
             for (int k = 0; k < nband; ++k) {
-                if (k == nband / 2) walk->push_back(0);
+                if (k == nband / 2) walk->push_back(-1);
                 for (int b = 0; b < nband; ++b)
-                    if (A->offsets[b] == sorted[k]) walk->push_back(b + 1);
+                    if (A->offsets[b] == sorted[k]) walk->push_back(b);
             }
         } else {
-            walk->push_back(0);
+            walk->push_back(-1);
             for (int b = 0; b < nband; ++b)
-                if (std::llabs((long long)A->offsets[b]) < (long long)ngrid) walk->push_back(b + 1);
+                if (std::llabs((long long)A->offsets[b]) < (long long)ngrid) walk->push_back(b);
         }
     }
     if (!canonical) return STR_G;
@@ -149,40 +147,24 @@ __global__ __launch_bounds__(BLOCK) void k_str_dinv_apply(int n, int nc, const d
     }
 }
 
-// device copy of a dSTRmat for the length of a call
-struct TmpSTR {
-    int     ngrid = 0, nc = 0, n = 0, nb1 = 0, form = ERROR_INPUT_PAR;
-    size_t  stride = 0;
+// device copy of a dSTRmat for the length of a call: the bands of str_plan's walk, the form, and the offsets where the kernel reads them
+struct TmpSTR : StrBands {
+    int     ngrid = 0, nc = 0, n = 0, form = ERROR_INPUT_PAR;
     int*    offs = nullptr;
-    double* val = nullptr;
+    DevPool pool;
     bool    ok = false;
     explicit TmpSTR(const dSTRmat* A)
     {
         std::vector<int> walk;
         form = str_plan(A, &walk);
         if (form < 0 || ctx_init() < 0) return;
-        ngrid = A->ngrid; nc = A->nc; n = ngrid * nc; nb1 = (int)walk.size();
-        const size_t nc2 = (size_t)nc * nc;
-        stride = ((size_t)ngrid * nc2 + 7) / 8 * 8;   // bands start on 64-byte boundaries
-        std::vector<int> ho((size_t)nb1);
-        if (hipMalloc(&offs, sizeof(int) * (size_t)nb1) != hipSuccess) return;
-        if (hipMalloc(&val, sizeof(double) * std::max<size_t>(stride * nb1, 1)) != hipSuccess) return;
-        if (hipMemset(val, 0, sizeof(double) * stride * nb1) != hipSuccess) return;
-        for (int k = 0; k < nb1; ++k) {
-            const int    off = walk[k] ? A->offsets[walk[k] - 1] : 0;
-            const size_t len = (size_t)ngrid - (size_t)std::abs(off), shift = off < 0 ? (size_t)(-off) : 0;   // a lower band is stored by column
-            const double* src = walk[k] ? A->offdiag[walk[k] - 1] : A->diag;
-            ho[(size_t)k] = off;
-            if (len && hipMemcpy(val + (size_t)k * stride + shift * nc2, src, sizeof(double) * len * nc2, hipMemcpyHostToDevice) != hipSuccess) return;
-        }
-        if (hipMemcpy(offs, ho.data(), sizeof(int) * (size_t)nb1, hipMemcpyHostToDevice) != hipSuccess) return;
+        ngrid = A->ngrid; nc = A->nc; n = ngrid * nc;
+        if (!init(pool, A, walk) || !pool.get(&offs, off.size())) return;
+        if (hipMemcpy(offs, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) != hipSuccess) return;
         ok = true;
     }
-    TmpSTR(const TmpSTR&) = delete;
-    TmpSTR& operator=(const TmpSTR&) = delete;
-    ~TmpSTR() { if (offs) (void)hipFree(offs); if (val) (void)hipFree(val); }
     // matrix bytes + x + y written (+ y read) of one product
-    double bytes(bool yin) const { return 8.0 * ((double)nb1 * ngrid * nc * nc + (double)n * (yin ? 3 : 2)); }
+    double bytes(bool yin) const { return 8.0 * ((double)nb * ngrid * nc * nc + (double)n * (yin ? 3 : 2)); }
 };
 
 template <int NC, int FORM, int NB1>
@@ -212,20 +194,11 @@ static void str_aAxpy(const TmpSTR& M, double alpha, const double* x, const doub
         return;
     }
     StrArgs a{};
-    a.ngrid = M.ngrid; a.n = M.n; a.nb1 = M.nb1; a.offs = M.offs; a.val = M.val; a.stride = M.stride;
+    a.ngrid = M.ngrid; a.n = M.n; a.nb1 = M.nb; a.offs = M.offs; a.val = M.val; a.stride = M.stride;
     a.x = x; a.yin = yin; a.yout = yout; a.alpha = alpha; a.beta = 1.0 / alpha;
     a.ntiles = (int)(((long long)M.n + BLOCK - 1) / BLOCK);
     a.per_xcd = (a.ntiles + 7) / 8;
-    switch (M.nc) {
-        case 1: launch_str_nc<1>(M.form, a); break;
-        case 2: launch_str_nc<2>(M.form, a); break;
-        case 3: launch_str_nc<3>(M.form, a); break;
-        case 4: launch_str_nc<4>(M.form, a); break;
-        case 5: launch_str_nc<5>(M.form, a); break;
-        case 6: launch_str_nc<6>(M.form, a); break;
-        case 7: launch_str_nc<7>(M.form, a); break;
-        default: break;
-    }
+    (void)str_for_nc(M.nc, [&](auto NC) { launch_str_nc<NC()>(M.form, a); return 0; });
 }
 static void str_mxv(const TmpSTR& M, const double* x, double* y) { str_aAxpy(M, 1.0, x, nullptr, y); }
 // r = b; r += (-1) A x: what the reference's solvers do (fasp_darray_cp, fasp_blas_dstr_aAxpy(-1.0, ...))

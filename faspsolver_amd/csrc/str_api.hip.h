@@ -65,13 +65,12 @@ short fasp_format_dstr_dcsr(const dSTRmat* A, dCSRmat* B)
 {
     FASP_ENTRY();
     if (!B || str_plan(A, nullptr) < 0) return ERROR_INPUT_PAR;
-    const int nc = A->nc, nc2 = nc * nc, ngrid = A->ngrid, nband = A->nband, rows = nc * ngrid;
+    const int nc = A->nc, ngrid = A->ngrid, nband = A->nband, rows = nc * ngrid;
     int* ia = (int*)fasp_mem_calloc((unsigned)rows + 1, sizeof(int));
-    auto has_term = [&](int i, int b) { const long long j = (long long)i + A->offsets[b]; return j >= 0 && j < ngrid; };
     long long nnz = 0;
     for (int i = 0; i < ngrid; ++i) {
         int blocks = 1;
-        for (int b = 0; b < nband; ++b) blocks += has_term(i, b) ? 1 : 0;
+        for (int b = 0; b < nband; ++b) blocks += str_block(A, b, i) ? 1 : 0;
         for (int p = 0; p < nc; ++p) {
             nnz += (long long)nc * blocks;
             if (nnz > 0x7fffffffLL) { fasp_mem_free(ia); return ERROR_INPUT_PAR; }
@@ -83,9 +82,9 @@ short fasp_format_dstr_dcsr(const dSTRmat* A, dCSRmat* B)
     for (int i = 0; i < ngrid; ++i) {
         int block = 0;
         for (int b = -1; b < nband; ++b) {
-            if (b >= 0 && !has_term(i, b)) continue;
-            const int     off = b < 0 ? 0 : A->offsets[b], col0 = (i + off) * nc;
-            const double* src = b < 0 ? A->diag + (size_t)i * nc2 : A->offdiag[b] + (size_t)(off < 0 ? i + off : i) * nc2;
+            const double* src = str_block(A, b, i);   // (b == -1: the diagonal block)
+            if (!src) continue;
+            const int col0 = (i + (b < 0 ? 0 : A->offsets[b])) * nc;
             for (int p = 0; p < nc; ++p) {
                 const size_t at = (size_t)ia[(size_t)i * nc + p] + (size_t)block * nc;
                 for (int q = 0; q < nc; ++q) { ja[at + q] = col0 + q; av[at + q] = src[p * nc + q]; }
@@ -135,17 +134,9 @@ double fasp_hip_time_str_mxv(const dSTRmat* A, int reps)
     TmpVec dx(nullptr, (size_t)M.n), dy(nullptr, (size_t)M.n);
     if (!dx.d || !dy.d) return -1.0;
     (void)hipMemsetAsync(dx.d, 0, sizeof(double) * dx.n, g_ctx.stream);
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     str_mxv(M, dx.d, dy.d); str_mxv(M, dx.d, dy.d);
-    (void)hipEventRecord(e0, g_ctx.stream);
-    for (int i = 0; i < reps; ++i) str_mxv(M, dx.d, dy.d);
-    (void)hipEventRecord(e1, g_ctx.stream);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return (double)ms / reps;
+    double ms = -1.0;
+    return time_reps(reps, [&] { str_mxv(M, dx.d, dy.d); return 0; }, &ms) < 0 ? -1.0 : ms;
 }
 
 // ---- structured ILU on the device: the dev entries (fasp_hip_dev.h) -------------------------------------
@@ -187,18 +178,11 @@ double fasp_hip_time_str_ilu(const dSTRmat* LU, int lfil, int reps)
     std::vector<double> hr(n);
     for (size_t i = 0; i < n; ++i) hr[i] = std::sin(0.37 * (double)i) + 0.1;
     if (hipMemcpy(M.r, hr.data(), sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) return -1.0;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
     if (str_ilu_apply(M, M.r, M.z) < 0) return -1.0;   // warm-up
-    (void)hipEventRecord(e0, g_ctx.stream);
-    for (int i = 0; i < reps; ++i) (void)str_ilu_apply(M, M.r, M.z);
-    (void)hipEventRecord(e1, g_ctx.stream);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (seq_err_check() < 0) return -1.0;
-    return (double)ms / reps;
+    double ms = -1.0;
+    const int st = time_reps(reps, [&] { return str_ilu_apply(M, M.r, M.z); }, &ms);
+    if (seq_err_check() < 0 || st < 0) return -1.0;
+    return ms;
 }
 
 // PreSTR.c:44 (host arrays): z_i = Dinv_i r_i, summed as fasp_blas_smat_mxv does (BlaSmallMat.c:238: from the first product for
@@ -409,18 +393,7 @@ int str_sweep_run(const char* fn, const dSTRmat* A, int kind, int order, const i
     if (!M.ok) return ERROR_ALLOC_MEM;
     int st = FASP_SUCCESS;
     for (int s = 0; s < nsweeps && st >= 0; ++s) st = M.sweep();
-    if (reps > 0 && st >= 0) {
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return ERROR_MISC;
-        (void)hipEventRecord(e0, g_ctx.stream);
-        for (int i = 0; i < reps && st >= 0; ++i) st = M.sweep();
-        (void)hipEventRecord(e1, g_ctx.stream);
-        (void)hipEventSynchronize(e1);
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, e0, e1);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (ms) *ms = (double)t / reps;
-    }
+    if (reps > 0 && ms && st >= 0) st = time_reps(reps, [&] { return M.sweep(); }, ms);
     if (hipStreamSynchronize(g_ctx.stream) != hipSuccess && st >= 0) st = ERROR_MISC;
     if (M.used_pipe && seq_err_check() < 0 && st >= 0) st = ERROR_MISC;   // a poll of the pipelined form that ran out
     if (st >= 0 && hipMemcpy(u, M.u, sizeof(double) * (size_t)P.D.ngrid * P.D.nc, hipMemcpyDeviceToHost) != hipSuccess) st = ERROR_MISC;
@@ -785,22 +758,12 @@ int fasp_hip_time_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const 
     std::vector<double> hb(n);
     for (size_t i = 0; i < n; ++i) hb[i] = std::sin(0.37 * (double)i) + 0.1;
     HIPCK(hipMemcpy(M.b, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1, e2, e3;
-    HIPCK(hipEventCreate(&e0)); HIPCK(hipEventCreate(&e1)); HIPCK(hipEventCreate(&e2)); HIPCK(hipEventCreate(&e3));
-    int st = FASP_SUCCESS;
-    HIPCK(hipEventRecord(e0, g_ctx.stream));
-    for (int i = 0; i < reps && st >= 0; ++i) st = M.launch_factor();
-    HIPCK(hipEventRecord(e1, g_ctx.stream));
+    double tf = 0.0, ts = 0.0;
+    int st = time_reps(reps, [&] { return M.launch_factor(); }, &tf);
     if (st >= 0) st = M.precond(M.b, M.u);   // warm-up
-    HIPCK(hipEventRecord(e2, g_ctx.stream));
-    for (int i = 0; i < reps && st >= 0; ++i) st = M.precond(M.b, M.u);
-    HIPCK(hipEventRecord(e3, g_ctx.stream));
-    HIPCK(hipEventSynchronize(e3));
-    float tf = 0.f, ts = 0.f;
-    (void)hipEventElapsedTime(&tf, e0, e1); (void)hipEventElapsedTime(&ts, e2, e3);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
+    if (st >= 0) st = time_reps(reps, [&] { return M.precond(M.b, M.u); }, &ts);
     str_swz_info(M, info);
-    if (ms_factor) *ms_factor = (double)tf / reps;
-    if (ms_sweep) *ms_sweep = (double)ts / reps;
+    if (ms_factor) *ms_factor = tf;
+    if (ms_sweep) *ms_sweep = ts;
     return st;
 }

@@ -11,8 +11,8 @@
 // lies in 0 .. ngrid-1; the two agree because the host checks at bind time (str_ilu_describe) that every coefficient of the other kind is
 // exactly 0.0 -- every grid-derived matrix gives that -- so z can differ from the reference's in the sign of a zero only.
 //
-// Layout: the evaluated bands index-free as in TmpSTR: band k `stride` doubles long, the block of grid point i at i nc^2 (a lower band is
-// stored by column in the dSTRmat: shifted here).  The offsets and the term geometry are a handful of integers in the kernel arguments.
+// Layout: every evaluated band of both triangles in a StrBands store of its own (str_common.hip.h).  The offsets and the term geometry are
+// a handful of integers in the kernel arguments.
 //
 // Schedule: level(i) = x + wy y + wz z with (wy, wz) = (1, 1) for ILU(0) and (2, 3) for ILU(1): every L term lowers the level by at least
 // one (ILU(1): -1, -1, -2, -1, -2, -3).  L runs the levels upwards, U downwards.  Lane = (grid point, component p); a wavefront holds
@@ -225,15 +225,11 @@ static bool str_ilu_describe(const dSTRmat* LU, int lfil, StrIluDesc& D, const c
     *why = "";
     if (!LU || (lfil != 0 && lfil != 1) || LU->ngrid <= 0 || LU->nc < 1 || LU->nc > 7 || !LU->diag || !LU->offsets || !LU->offdiag) { *why = "not a factor (NULL or zeroed, or nc outside 1 .. 7)"; return false; }
     if ((long long)LU->ngrid * LU->nc * LU->nc > 0x7fffffffLL) { *why = "too large"; return false; }
-    int nline, nplane;
-    if (LU->nx == 1) { nline = LU->ny; nplane = LU->ngrid; }
-    else if (LU->ny == 1 || LU->nz == 1) { nline = LU->nx; nplane = LU->ngrid; }
-    else { nline = LU->nx; nplane = LU->nxy; }
-    const int ngrid = LU->ngrid, nc2 = LU->nc * LU->nc;
-    if (nline < 2 || nline >= ngrid || ngrid % nline || nplane % nline || ngrid % nplane) { *why = "degenerate grid"; return false; }
+    StrGrid G;
+    if (!str_grid(LU, G, why)) return false;
+    const int ngrid = LU->ngrid, nline = G.nline, nplane = G.nplane;
     D.ngrid = ngrid; D.nc = LU->nc; D.lfil = lfil;
-    D.gx = nline; D.gy = nplane / nline; D.gz = ngrid / nplane;
-    if (D.gz == 1) { D.gy = ngrid / nline; }
+    D.gx = G.gx; D.gy = G.gy; D.gz = G.gz;
     const bool three_d = D.gz > 1;
     D.wy = lfil ? 2 : 1; D.wz = lfil ? 3 : 1;
     // the L terms in the reference's order: (slot, dx, dy, dz); U: slot + 1, mirrored
@@ -254,24 +250,10 @@ static bool str_ilu_describe(const dSTRmat* LU, int lfil, StrIluDesc& D, const c
         const bool evaluated = three_d || T[3] == 0; // on a 2-D grid the plane terms reach no geometric neighbour
         for (int u = 0; u < 2; ++u) {
             const int slot = T[0] + u, sg = u ? -1 : 1, dx = sg * T[1], dy = sg * T[2], dz = sg * T[3];
-            const int off = LU->offsets[slot];
-            const double* band = LU->offdiag[slot];
-            // every coefficient the reference would use between points that are not geometric neighbours must be exactly 0.0
-            const int lo = off < 0 ? -off : 0, hi = off < 0 ? ngrid : ngrid - off;
-            for (int i = lo; i < hi; ++i) {
-                const int x = i % D.gx, y = (i / D.gx) % D.gy, z = i / (D.gx * D.gy);
-                const bool geo = evaluated && (unsigned)(x + dx) < (unsigned)D.gx && (unsigned)(y + dy) < (unsigned)D.gy && (unsigned)(z + dz) < (unsigned)D.gz;
-                if (geo) {
-                    if (i + off != (x + dx) + D.gx * ((y + dy) + D.gy * (z + dz))) { *why = "offsets do not match the grid"; return false; }
-                    continue;
-                }
-                const double* c = band + (size_t)(off < 0 ? i + off : i) * nc2;
-                for (int e = 0; e < nc2; ++e)
-                    if (!(c[e] == 0.0)) { *why = "a non-zero (or NaN) coefficient between grid points that are not geometric neighbours"; return false; }
-            }
+            if (!str_offgrid_coefficients_are_zero(LU, G, slot, dx, dy, dz, evaluated, why)) return false;
             if (evaluated) {
                 const int k2 = D.nt;
-                D.slot[u][k2] = slot; D.off[u][k2] = off; D.dx[u][k2] = dx; D.dy[u][k2] = dy; D.dz[u][k2] = dz;
+                D.slot[u][k2] = slot; D.off[u][k2] = LU->offsets[slot]; D.dx[u][k2] = dx; D.dy[u][k2] = dy; D.dz[u][k2] = dz;
             }
         }
         if (evaluated) { ++D.nt; if (T[3] != 0) ++D.ncross; }
@@ -292,52 +274,28 @@ static int str_ilu_plan(const StrIluDesc& D)
 
 struct StrIluDev {
     StrIluDesc D;
-    size_t   stride = 0;
-    double*  band[2][6] = {};
+    DevPool  pool;
+    StrBands B[2][6];                     // [0: L, 1: U][k]: term k, a store of one band each (see the constructor)
     double*  diag = nullptr, *y = nullptr, *z = nullptr, *r = nullptr;
     unsigned* sync = nullptr;
-    std::vector<void*> owned;
     std::vector<int> lvl_zlo, lvl_npts;   // level launches: first plane and points enumerated (gy per plane) of each level
     bool ok = false;
     bool used_pipe = false;
-    template <class T> bool get(T** dst, size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) return false;
-        owned.push_back(p);
-        *dst = static_cast<T*>(p);
-        return true;
-    }
     StrIluDev(const dSTRmat* LU, const StrIluDesc& desc) : D(desc)
     {
         if (ctx_init() < 0) return;
         const size_t nc2 = (size_t)D.nc * D.nc, n = (size_t)D.ngrid * D.nc;
-        stride = ((size_t)D.ngrid * nc2 + 7) / 8 * 8;
-        if (!get(&diag, stride) || !get(&y, n) || !get(&z, n) || !get(&r, n) || !get(&sync, 16)) return;
+        if (!pool.get(&diag, (size_t)D.ngrid * nc2) || !pool.get(&y, n) || !pool.get(&z, n) || !pool.get(&r, n) || !pool.get(&sync, 16)) return;
         if (hipMemcpy(diag, LU->diag, sizeof(double) * (size_t)D.ngrid * nc2, hipMemcpyHostToDevice) != hipSuccess) return;
+        // One allocation per band, not one store over the 2 nt picks: with a triangle's bands exactly `stride` apart the level form measured
+        // 1.7 % slower on P7(128), nc 1 (stride 16 MiB) and 1.6 % faster on P7(256) (profiles/str_refactor_ab.txt); this keeps both as they were.
         for (int u = 0; u < 2; ++u)
-            for (int k = 0; k < D.nt; ++k) {
-                const int off = D.off[u][k];
-                const size_t len = (size_t)D.ngrid - (size_t)std::abs(off), shift = off < 0 ? (size_t)(-off) : 0;
-                if (!get(&band[u][k], stride)) return;
-                if (hipMemset(band[u][k], 0, sizeof(double) * stride) != hipSuccess) return;
-                if (hipMemcpy(band[u][k] + shift * nc2, LU->offdiag[D.slot[u][k]], sizeof(double) * len * nc2, hipMemcpyHostToDevice) != hipSuccess) return;
-            }
-        const unsigned sync0[16] = {};
-        if (hipMemcpy(sync, sync0, sizeof(sync0), hipMemcpyHostToDevice) != hipSuccess) return;
-        const unsigned long long herr_addr = (unsigned long long)seq_err_device_word();
-        if (hipMemcpy(sync + 6, &herr_addr, 8, hipMemcpyHostToDevice) != hipSuccess) return;
-        const int inplane = (D.gx - 1) + D.wy * (D.gy - 1), nlev = inplane + D.wz * (D.gz - 1) + 1;
-        lvl_zlo.resize((size_t)nlev); lvl_npts.resize((size_t)nlev);
-        for (int l = 0; l < nlev; ++l) {
-            const int zlo = l > inplane ? (l - inplane + D.wz - 1) / D.wz : 0, zhi = std::min(D.gz - 1, l / D.wz);
-            lvl_zlo[(size_t)l] = zlo; lvl_npts[(size_t)l] = (zhi - zlo + 1) * D.gy;
-        }
+            for (int k = 0; k < D.nt; ++k)
+                if (!B[u][k].init(pool, LU, {D.slot[u][k]})) return;
+        if (!str_sync_words(sync)) return;
+        str_diag_levels(D.gx, D.gy, D.gz, D.wy, D.wz, lvl_zlo, lvl_npts);
         ok = true;
     }
-    StrIluDev(const StrIluDev&) = delete;
-    StrIluDev& operator=(const StrIluDev&) = delete;
-    ~StrIluDev() { for (void* p : owned) (void)hipFree(p); }
     // matrix values of both triangles and the pivots, the right-hand side read, y written and read, z written
     double bytes() const { return 8.0 * ((2.0 * D.nt + 1.0) * D.ngrid * D.nc * D.nc + 4.0 * D.ngrid * D.nc); }
 };
@@ -380,24 +338,14 @@ static int str_ilu_apply(StrIluDev& M, const double* in, double* out)
     for (int u = 0; u < 2; ++u) {
         StrTriArgs a{};
         for (int k = 0; k < M.D.nt; ++k) {
-            a.band[k] = M.band[u][k]; a.off[k] = M.D.off[u][k];
+            a.band[k] = M.B[u][k].val; a.off[k] = M.D.off[u][k];
             a.dx[k] = M.D.dx[u][k]; a.dy[k] = M.D.dy[u][k]; a.dz[k] = M.D.dz[u][k];
         }
         a.diag = M.diag; a.in = u ? M.y : in; a.out = u ? out : M.y;
         a.nt = M.D.nt; a.ncross = M.D.ncross;
         a.gx = M.D.gx; a.gy = M.D.gy; a.gz = M.D.gz; a.wy = M.D.wy; a.wz = M.D.wz;
         a.sync = M.sync;
-        int st = ERROR_INPUT_PAR;
-        switch (M.D.nc) {
-            case 1: st = str_tri_solve_nc<1>(M, form, u != 0, a); break;
-            case 2: st = str_tri_solve_nc<2>(M, form, u != 0, a); break;
-            case 3: st = str_tri_solve_nc<3>(M, form, u != 0, a); break;
-            case 4: st = str_tri_solve_nc<4>(M, form, u != 0, a); break;
-            case 5: st = str_tri_solve_nc<5>(M, form, u != 0, a); break;
-            case 6: st = str_tri_solve_nc<6>(M, form, u != 0, a); break;
-            case 7: st = str_tri_solve_nc<7>(M, form, u != 0, a); break;
-            default: break;
-        }
+        const int st = str_for_nc(M.D.nc, [&](auto NC) { return str_tri_solve_nc<NC()>(M, form, u != 0, a); });
         if (st < 0) return st;
     }
     return FASP_SUCCESS;

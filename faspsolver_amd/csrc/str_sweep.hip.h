@@ -11,9 +11,8 @@
 //   Jacobi: every term reads the vector as it came in, then the closing step of GS.
 // No fused multiply-add (-ffp-contract=off).
 //
-// Layout: the bands that have terms, in storage order, each `stride` doubles long, the block of grid point i at i nc^2 whatever the offset (a
-// lower band is stored by column in the dSTRmat: shifted here), as in TmpSTR.  No matrix index arrays.  Lane = (grid point, component p); a
-// wavefront holds 64 / nc whole points, so that the closing product takes rhs's other components by a shuffle (as k_str_tri).
+// Layout: the bands that have terms, in storage order, in a StrBands store (str_common.hip.h).  No matrix index arrays.  Lane = (grid point,
+// component p); a wavefront holds 64 / nc whole points, so that the closing product takes rhs's other components by a shuffle (as k_str_tri).
 //
 // Forms of a GS / SOR sweep (str_sweep_plan is the one place that chooses):
 //   level    ASCEND / DESCEND on a grid-like matrix.  Level x + y + z, one launch per level, the points of a level enumerated from (y, z), in
@@ -297,40 +296,21 @@ static int str_sweep_describe(const dSTRmat* A, StrSweepDesc& D)
 {
     if (str_plan(A, nullptr) < 0) return ERROR_INPUT_PAR;
     if ((long long)A->ngrid * A->nc * A->nc > 0x7fffffffLL) return ERROR_INPUT_PAR;
-    const int ngrid = A->ngrid, nc2 = A->nc * A->nc;
+    const int ngrid = A->ngrid;
     D.ngrid = ngrid; D.nc = A->nc;
     for (int b = 0; b < A->nband; ++b)
         if (std::llabs((long long)A->offsets[b]) < (long long)ngrid) { D.slot.push_back(b); D.off.push_back(A->offsets[b]); }
     D.nb = (int)D.slot.size();
     D.dx.assign((size_t)D.nb, 0); D.dy.assign((size_t)D.nb, 0); D.dz.assign((size_t)D.nb, 0);
     D.geo = false;
-    int nline, nplane;
-    if (A->nx == 1) { nline = A->ny; nplane = ngrid; }
-    else if (A->ny == 1 || A->nz == 1) { nline = A->nx; nplane = ngrid; }
-    else { nline = A->nx; nplane = A->nxy; }
-    if (nline < 2 || nline >= ngrid || ngrid % nline || nplane < nline || nplane % nline || ngrid % nplane) { D.why = "degenerate grid"; return FASP_SUCCESS; }
-    D.gx = nline; D.gy = nplane / nline; D.gz = ngrid / nplane;
+    StrGrid G;
+    if (!str_grid(A, G, &D.why)) return FASP_SUCCESS;
+    D.gx = G.gx; D.gy = G.gy; D.gz = G.gz;
     if (D.nb > 6) { D.why = "an offset outside {+-1, +-nline, +-nplane}"; return FASP_SUCCESS; }
-    for (int k = 0; k < D.nb; ++k) {
-        const int off = D.off[(size_t)k], m = std::abs(off), sg = off < 0 ? -1 : 1;
-        if (m == 1) D.dx[(size_t)k] = sg;
-        else if (m == nline) D.dy[(size_t)k] = sg;
-        else if (m == nplane && D.gz > 1) D.dz[(size_t)k] = sg;
-        else { D.why = "an offset outside {+-1, +-nline, +-nplane}"; return FASP_SUCCESS; }
-    }
-    // every coefficient the reference would use between points that are not geometric neighbours must be exactly 0.0
-    for (int k = 0; k < D.nb; ++k) {
-        const int off = D.off[(size_t)k], dx = D.dx[(size_t)k], dy = D.dy[(size_t)k], dz = D.dz[(size_t)k];
-        const double* band = A->offdiag[D.slot[(size_t)k]];
-        const int lo = off < 0 ? -off : 0, hi = off < 0 ? ngrid : ngrid - off;
-        for (int i = lo; i < hi; ++i) {
-            const int x = i % D.gx, y = (i / D.gx) % D.gy, z = i / (D.gx * D.gy);
-            if ((unsigned)(x + dx) < (unsigned)D.gx && (unsigned)(y + dy) < (unsigned)D.gy && (unsigned)(z + dz) < (unsigned)D.gz) continue;
-            const double* c = band + (size_t)(off < 0 ? i + off : i) * nc2;
-            for (int e = 0; e < nc2; ++e)
-                if (!(c[e] == 0.0)) { D.why = "a non-zero (or NaN) coefficient between grid points that are not geometric neighbours"; return FASP_SUCCESS; }
-        }
-    }
+    for (size_t k = 0; k < (size_t)D.nb; ++k)
+        if (!G.classify(D.off[k], D.dx[k], D.dy[k], D.dz[k])) { D.why = "an offset outside {+-1, +-nline, +-nplane}"; return FASP_SUCCESS; }
+    for (size_t k = 0; k < (size_t)D.nb; ++k)
+        if (!str_offgrid_coefficients_are_zero(A, G, D.slot[k], D.dx[k], D.dy[k], D.dz[k], true, &D.why)) return FASP_SUCCESS;
     D.geo = true;
     return FASP_SUCCESS;
 }
@@ -363,36 +343,21 @@ static void str_sweep_visits(int ngrid, int order, const int* mark, bool cf, boo
     else for (int i = ngrid - 1; i >= 0; --i) seq.push_back(i);
 }
 
-// level(v) = 1 + the largest level among the earlier visits that wrote a point v reads, that read the point v writes, or that wrote the
-// same point (-1: none).  One pass with two arrays per point.  Returns the number of levels.
+// The levels of the visits (str_visit_levels): a visit writes its grid point and reads the points its existing terms reach -- the geometric
+// neighbours of a grid-like matrix, otherwise those of the index rule.  Returns the number of levels.
 static int str_sweep_levels(const StrSweepDesc& D, const std::vector<int>& seq, std::vector<int>& lev)
 {
-    std::vector<int> lw((size_t)std::max(D.ngrid, 1), -1), mr((size_t)std::max(D.ngrid, 1), -1);
-    lev.resize(seq.size());
-    int nlev = 0;
-    std::vector<int> nbr((size_t)std::max(D.nb, 1));
-    const int plane = D.gx * D.gy;
-    for (size_t v = 0; v < seq.size(); ++v) {
-        const int i = seq[v] & 0x7fffffff;
-        int L = std::max(lw[(size_t)i], mr[(size_t)i]);
-        int x = 0, y = 0, z = 0;
-        if (D.geo) { x = i % D.gx; y = (i / D.gx) % D.gy; z = i / plane; }
-        int nn = 0;
-        for (int k = 0; k < D.nb; ++k) {
-            const long long j = (long long)i + D.off[(size_t)k];
-            const bool ex = D.geo ? (unsigned)(x + D.dx[(size_t)k]) < (unsigned)D.gx && (unsigned)(y + D.dy[(size_t)k]) < (unsigned)D.gy &&
-                                        (unsigned)(z + D.dz[(size_t)k]) < (unsigned)D.gz
+    auto writes = [&](size_t v, auto&& f) { f(seq[v] & 0x7fffffff); };
+    auto reads = [&](size_t v, auto&& f) {
+        const int i = seq[v] & 0x7fffffff, x = D.geo ? i % D.gx : 0, y = D.geo ? (i / D.gx) % D.gy : 0, z = D.geo ? i / (D.gx * D.gy) : 0;
+        for (size_t k = 0; k < (size_t)D.nb; ++k) {
+            const long long j = (long long)i + D.off[k];
+            const bool ex = D.geo ? (unsigned)(x + D.dx[k]) < (unsigned)D.gx && (unsigned)(y + D.dy[k]) < (unsigned)D.gy && (unsigned)(z + D.dz[k]) < (unsigned)D.gz
                                   : j >= 0 && j < D.ngrid;
-            if (!ex) continue;
-            L = std::max(L, lw[(size_t)j]);
-            nbr[(size_t)nn++] = (int)j;
+            if (ex) f((int)j);
         }
-        ++L;
-        lev[v] = L; lw[(size_t)i] = L;
-        for (int q = 0; q < nn; ++q) mr[(size_t)nbr[(size_t)q]] = std::max(mr[(size_t)nbr[(size_t)q]], L);
-        nlev = std::max(nlev, L + 1);
-    }
-    return nlev;
+    };
+    return str_visit_levels(D.ngrid, seq.size(), writes, reads, lev);
 }
 
 // a sweep resident on the device: matrix, plan and vectors uploaded once
@@ -401,24 +366,16 @@ struct StrSweepDev {
     int      kind = STR_SWEEP_GS, form = STR_SWF_LIST;
     bool     desc = false;
     double   w = 1.0;
-    size_t   stride = 0;
-    double*  val = nullptr, *diag = nullptr, *b = nullptr, *u = nullptr, *u2 = nullptr;
+    DevPool  pool;
+    StrBands B;                           // the bands D.slot
+    double*  diag = nullptr, *b = nullptr, *u = nullptr, *u2 = nullptr;
     int*     terms = nullptr, *list = nullptr;
     unsigned* sync = nullptr;
-    std::vector<void*> owned;
     std::vector<int> lvl_zlo, lvl_npts;   // level form: first plane and points enumerated (gy per plane) of each level
     std::vector<int> lvl_first;           // ordered form: the slice of each level in the list (nlev + 1 entries)
     int      kindk[6] = {}, kcross = -1;
     bool     ok = false, used_pipe = false;
     int      launches = 0, levels = 0, wgs = 0, visits = 0;
-    template <class T> bool get(T** dst, size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) return false;
-        owned.push_back(p);
-        *dst = static_cast<T*>(p);
-        return true;
-    }
     // dg: the diagonal (nc == 1) or the inverted diagonal blocks; seq: the visits (ordered form only)
     StrSweepDev(const dSTRmat* A, const StrSweepDesc& desc_, int kind_, int form_, bool descending, double weight, const double* dg,
                 const std::vector<int>& seq, const double* hb, const double* hu)
@@ -426,33 +383,20 @@ struct StrSweepDev {
     {
         if (ctx_init() < 0) return;
         const size_t nc2 = (size_t)D.nc * D.nc, n = (size_t)D.ngrid * D.nc;
-        stride = ((size_t)D.ngrid * nc2 + 7) / 8 * 8;
-        if (!get(&val, stride * (size_t)std::max(D.nb, 1)) || !get(&diag, stride) || !get(&b, n) || !get(&u, n) || !get(&u2, n) || !get(&sync, 16) ||
-            !get(&terms, 4 * (size_t)std::max(D.nb, 1)))
+        if (!B.init(pool, A, D.slot)) return;
+        if (!pool.get(&diag, B.stride) || !pool.get(&b, n) || !pool.get(&u, n) || !pool.get(&u2, n) || !pool.get(&sync, 16) ||
+            !pool.get(&terms, 4 * (size_t)std::max(D.nb, 1)))
             return;
-        if (D.nb && hipMemset(val, 0, sizeof(double) * stride * (size_t)D.nb) != hipSuccess) return;
         std::vector<int> ht(4 * (size_t)std::max(D.nb, 1), 0);
-        for (int k = 0; k < D.nb; ++k) {
-            const int off = D.off[(size_t)k];
-            const size_t len = (size_t)D.ngrid - (size_t)std::abs(off), shift = off < 0 ? (size_t)(-off) : 0;   // a lower band is stored by column
-            if (hipMemcpy(val + (size_t)k * stride + shift * nc2, A->offdiag[D.slot[(size_t)k]], sizeof(double) * len * nc2, hipMemcpyHostToDevice) != hipSuccess) return;
-            ht[4 * (size_t)k] = off; ht[4 * (size_t)k + 1] = D.dx[(size_t)k]; ht[4 * (size_t)k + 2] = D.dy[(size_t)k]; ht[4 * (size_t)k + 3] = D.dz[(size_t)k];
-        }
+        for (size_t k = 0; k < (size_t)D.nb; ++k) { ht[4 * k] = D.off[k]; ht[4 * k + 1] = D.dx[k]; ht[4 * k + 2] = D.dy[k]; ht[4 * k + 3] = D.dz[k]; }
         if (hipMemcpy(terms, ht.data(), sizeof(int) * ht.size(), hipMemcpyHostToDevice) != hipSuccess) return;
         if (hipMemcpy(diag, dg, sizeof(double) * (size_t)D.ngrid * nc2, hipMemcpyHostToDevice) != hipSuccess) return;
         if (hipMemcpy(b, hb, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) return;
         if (hipMemcpy(u, hu, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) return;
-        unsigned sync0[16] = {};
-        const unsigned long long herr_addr = (unsigned long long)seq_err_device_word();
-        std::memcpy(sync0 + 6, &herr_addr, 8);
-        if (hipMemcpy(sync, sync0, sizeof(sync0), hipMemcpyHostToDevice) != hipSuccess) return;
+        if (!str_sync_words(sync)) return;
         if (form == STR_SWF_LEVEL || form == STR_SWF_PIPE) {
-            const int inplane = (D.gx - 1) + (D.gy - 1), nlev = inplane + (D.gz - 1) + 1;
-            lvl_zlo.resize((size_t)nlev); lvl_npts.resize((size_t)nlev);
-            for (int l = 0; l < nlev; ++l) {
-                const int zlo = l > inplane ? l - inplane : 0, zhi = std::min(D.gz - 1, l);
-                lvl_zlo[(size_t)l] = zlo; lvl_npts[(size_t)l] = (zhi - zlo + 1) * D.gy;
-            }
+            str_diag_levels(D.gx, D.gy, D.gz, 1, 1, lvl_zlo, lvl_npts);
+            const int nlev = (int)lvl_zlo.size();
             for (int k = 0; k < D.nb; ++k) {   // a term is new iff its partner lies one level towards where the sweep comes from
                 const int step = D.dx[(size_t)k] + D.dy[(size_t)k] + D.dz[(size_t)k];
                 const bool is_new = step == (desc ? 1 : -1);
@@ -461,15 +405,11 @@ struct StrSweepDev {
             }
             levels = nlev; visits = D.ngrid;
         } else if (form == STR_SWF_LIST) {
-            std::vector<int> lev;
+            std::vector<int> lev, hl;
             const int nlev = str_sweep_levels(D, seq, lev);
-            lvl_first.assign((size_t)nlev + 1, 0);
-            for (size_t v = 0; v < seq.size(); ++v) ++lvl_first[(size_t)lev[v] + 1];
-            for (int l = 0; l < nlev; ++l) lvl_first[(size_t)l + 1] += lvl_first[(size_t)l];
-            std::vector<int> at(lvl_first.begin(), lvl_first.end() - 1), hl(std::max<size_t>(seq.size(), 1), 0);
-            for (size_t v = 0; v < seq.size(); ++v) hl[(size_t)at[(size_t)lev[v]]++] = seq[v];   // stable
-            if (!get(&list, hl.size())) return;
-            if (hipMemcpy(list, hl.data(), sizeof(int) * hl.size(), hipMemcpyHostToDevice) != hipSuccess) return;
+            str_bucket_by_level(seq, lev, nlev, lvl_first, hl, nullptr);
+            if (!pool.get(&list, hl.size())) return;
+            if (!hl.empty() && hipMemcpy(list, hl.data(), sizeof(int) * hl.size(), hipMemcpyHostToDevice) != hipSuccess) return;
             levels = nlev; visits = (int)seq.size();
         } else {
             levels = 1; visits = D.ngrid;
@@ -477,14 +417,11 @@ struct StrSweepDev {
         if (hipDeviceSynchronize() != hipSuccess) return;
         ok = true;
     }
-    StrSweepDev(const StrSweepDev&) = delete;
-    StrSweepDev& operator=(const StrSweepDev&) = delete;
-    ~StrSweepDev() { for (void* p : owned) (void)hipFree(p); }
 
     StrSweepArgs args() const
     {
         StrSweepArgs a{};
-        a.val = val; a.stride = stride; a.diag = diag; a.b = b; a.in = u; a.out = u;
+        a.val = B.val; a.stride = B.stride; a.diag = diag; a.b = b; a.in = u; a.out = u;
         a.terms = terms; a.list = list; a.nb = D.nb; a.ngrid = D.ngrid; a.geo = D.geo ? 1 : 0;
         for (int k = 0; k < std::min(D.nb, 6); ++k) {
             a.off[k] = D.off[(size_t)k]; a.dx[k] = D.dx[(size_t)k]; a.dy[k] = D.dy[(size_t)k]; a.dz[k] = D.dz[(size_t)k]; a.kind[k] = kindk[k];
@@ -539,16 +476,7 @@ struct StrSweepDev {
     {
         if (D.ngrid <= 0) return FASP_SUCCESS;
         if (form == STR_SWF_PIPE && seq_err_pending()) return seq_err_check();
-        switch (D.nc) {
-            case 1: return sweep_k<1>();
-            case 2: return sweep_k<2>();
-            case 3: return sweep_k<3>();
-            case 4: return sweep_k<4>();
-            case 5: return sweep_k<5>();
-            case 6: return sweep_k<6>();
-            case 7: return sweep_k<7>();
-            default: return ERROR_INPUT_PAR;
-        }
+        return str_for_nc(D.nc, [&](auto NC) { return sweep_k<NC()>(); });
     }
     // what a sweep moves at least: the matrix, the diagonal (blocks), b, u read and written
     double bytes() const { return 8.0 * (((double)D.nb + 1.0) * D.ngrid * D.nc * D.nc + 3.0 * D.ngrid * D.nc); }

@@ -260,49 +260,30 @@ struct StrSwzPlan {
     int levels = 0, widest = 0;
 };
 
-// level of every visit (header); returns the number of levels
+// level of every visit (header, str_visit_levels); returns the number of levels
 static int str_swz_levels(const dSTRmat* A, const StrSwzPlan& P, std::vector<int>& lev)
 {
     const int ngrid = P.ngrid, nc2 = P.nc * P.nc, nband = A->nband;
     // the points every row has a term to whose coefficient block is not all 0.0
     std::vector<int> rd((size_t)std::max(ngrid, 1) * (size_t)std::max(nband, 1)), nrd((size_t)std::max(ngrid, 1), 0);
-    for (int bnd = 0; bnd < nband; ++bnd) {
-        const long long off = A->offsets[bnd];
-        if (std::llabs(off) >= (long long)ngrid) continue;
-        const int lo = off < 0 ? (int)-off : 0, hi = off < 0 ? ngrid : ngrid - (int)off;
-        for (int i = lo; i < hi; ++i) {
-            const double* c = A->offdiag[bnd] + (size_t)(off < 0 ? i + off : i) * nc2;   // a lower band is stored by column
-            bool zero = true;
-            for (int e = 0; e < nc2 && zero; ++e) zero = c[e] == 0.0;
-            if (!zero) rd[(size_t)i * nband + nrd[(size_t)i]++] = (int)(i + off);
+    for (int bnd = 0; bnd < nband; ++bnd)
+        for (int i = 0; i < ngrid; ++i) {
+            const double* c = str_block(A, bnd, i);
+            if (c && !str_block_is_zero(c, nc2)) rd[(size_t)i * nband + nrd[(size_t)i]++] = i + A->offsets[bnd];
         }
-    }
-    std::vector<int> lw((size_t)std::max(ngrid, 1), -1), mr((size_t)std::max(ngrid, 1), -1), mem((size_t)P.nneigh + 1);
-    lev.resize(P.seq.size());
-    int nlev = 0;
-    for (size_t v = 0; v < P.seq.size(); ++v) {
+    auto members = [&](size_t v, auto&& f) {
         const int i = P.seq[v];
-        int k = 0;
-        mem[(size_t)k++] = i;
+        f(i);
         for (int l = 0; l < P.nneigh; ++l)
-            if (P.neigh[(size_t)i * P.nneigh + l] >= 0) mem[(size_t)k++] = P.neigh[(size_t)i * P.nneigh + l];
-        int L = -1;
-        for (int a = 0; a < k; ++a) {
-            const int p = mem[(size_t)a];
-            L = std::max(L, std::max(lw[(size_t)p], mr[(size_t)p]));
-            for (int q = 0; q < nrd[(size_t)p]; ++q) L = std::max(L, lw[(size_t)rd[(size_t)p * nband + q]]);
-        }
-        ++L;
-        lev[v] = L;
-        for (int a = 0; a < k; ++a) {
-            const int p = mem[(size_t)a];
-            lw[(size_t)p] = L;
-            mr[(size_t)p] = std::max(mr[(size_t)p], L);
-            for (int q = 0; q < nrd[(size_t)p]; ++q) { int& r = mr[(size_t)rd[(size_t)p * nband + q]]; r = std::max(r, L); }
-        }
-        nlev = std::max(nlev, L + 1);
-    }
-    return nlev;
+            if (P.neigh[(size_t)i * P.nneigh + l] >= 0) f(P.neigh[(size_t)i * P.nneigh + l]);
+    };
+    auto reads = [&](size_t v, auto&& f) {
+        members(v, [&](int p) {
+            f(p);
+            for (int q = 0; q < nrd[(size_t)p]; ++q) f(rd[(size_t)p * nband + q]);
+        });
+    };
+    return str_visit_levels(ngrid, P.seq.size(), members, reads, lev);
 }
 
 // Fills P.  fn: refusals are reported under this name.  with_levels false: the visits keep their order in one slice (factorisation only).
@@ -354,15 +335,7 @@ static int str_swz_plan(const char* fn, const dSTRmat* A, const ivector* neigh, 
     }
     if (with_levels) P.levels = str_swz_levels(A, P, P.lev);
     else { P.lev.assign(P.seq.size(), 0); P.levels = P.seq.empty() ? 0 : 1; }
-    P.lvl_first.assign((size_t)P.levels + 1, 0);
-    for (size_t v = 0; v < P.seq.size(); ++v) ++P.lvl_first[(size_t)P.lev[v] + 1];
-    for (int l = 0; l < P.levels; ++l) {
-        P.widest = std::max(P.widest, P.lvl_first[(size_t)l + 1]);
-        P.lvl_first[(size_t)l + 1] += P.lvl_first[(size_t)l];
-    }
-    std::vector<int> at(P.lvl_first.begin(), P.lvl_first.end() - 1);
-    P.list.assign(P.seq.size(), 0);
-    for (size_t v = 0; v < P.seq.size(); ++v) P.list[(size_t)at[(size_t)P.lev[v]]++] = P.seq[v];   // stable
+    str_bucket_by_level(P.seq, P.lev, P.levels, P.lvl_first, P.list, &P.widest);
     return FASP_SUCCESS;
 }
 
@@ -400,19 +373,11 @@ struct StrSwzDev {
     double*    fac = nullptr, *b = nullptr, *u = nullptr;
     unsigned*  count = nullptr;
     size_t     nslot64 = 0, nfac = 0, npiv = 0;
-    std::vector<void*> owned;
+    DevPool    pool;
     bool       ok = false;
     int        st = ERROR_ALLOC_MEM;       // why not ok
     int        nswap = 0, nstopped = 0;    // patches with a row interchange, patches that stopped (device factorisation)
     int        launches = 0;
-    template <class T> bool get(T** dst, size_t count_)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(T) * std::max<size_t>(count_, 1)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        owned.push_back(p);
-        *dst = static_cast<T*>(p);
-        return true;
-    }
     // diaginv / pivot: a caller's factors (checked by str_swz_check_factors), repacked; both NULL: factored here, on the device
     StrSwzDev(const dSTRmat* A, StrSwzPlan&& plan, const dvector* diaginv, const ivector* pivot) : P(std::move(plan)), M(A)
     {
@@ -421,10 +386,10 @@ struct StrSwzDev {
         nslot64 = (nslots + 63) / 64 * 64;
         if (ms2 && nslot64 > (size_t)0x7fffffffffffLL / (8 * ms2)) return;
         nfac = nslot64 * ms2; npiv = nslot64 * (size_t)P.ms;
-        std::vector<int> ho((size_t)M.nb1);
-        if (hipMemcpy(ho.data(), M.offs, sizeof(int) * (size_t)M.nb1, hipMemcpyDeviceToHost) != hipSuccess) return;
-        for (int k = 0; k < M.nb1; ++k) if (ho[(size_t)k] == 0) kdiag = k;
-        if (!get(&neigh, P.neigh.size()) || !get(&list, nslots) || !get(&piv, npiv) || !get(&fac, nfac) || !get(&b, n) || !get(&u, n) || !get(&count, 4)) return;
+        for (int k = 0; k < M.nb; ++k) if (M.off[(size_t)k] == 0) kdiag = k;
+        if (!pool.get(&neigh, P.neigh.size()) || !pool.get(&list, nslots) || !pool.get(&piv, npiv) || !pool.get(&fac, nfac) || !pool.get(&b, n) ||
+            !pool.get(&u, n) || !pool.get(&count, 4))
+            return;
         if (!P.neigh.empty() && hipMemcpy(neigh, P.neigh.data(), sizeof(int) * P.neigh.size(), hipMemcpyHostToDevice) != hipSuccess) return;
         if (nslots && hipMemcpy(list, P.list.data(), sizeof(int) * nslots, hipMemcpyHostToDevice) != hipSuccess) return;
         if (hipMemset(count, 0, sizeof(unsigned) * 4) != hipSuccess) return;
@@ -442,14 +407,11 @@ struct StrSwzDev {
         } else if (factor() < 0) { st = ERROR_MISC; return; }
         ok = true; st = FASP_SUCCESS;
     }
-    StrSwzDev(const StrSwzDev&) = delete;
-    StrSwzDev& operator=(const StrSwzDev&) = delete;
-    ~StrSwzDev() { for (void* p : owned) (void)hipFree(p); }
 
     StrSwzArgs args(const double* rhs, double* sol) const
     {
         StrSwzArgs a{};
-        a.val = M.val; a.stride = M.stride; a.offs = M.offs; a.nb1 = M.nb1; a.kdiag = kdiag; a.form = M.form; a.ngrid = P.ngrid;
+        a.val = M.val; a.stride = M.stride; a.offs = M.offs; a.nb1 = M.nb; a.kdiag = kdiag; a.form = M.form; a.ngrid = P.ngrid;
         a.neigh = neigh; a.nneigh = P.nneigh; a.list = list; a.fac = fac; a.piv = piv; a.ms = P.ms; a.b = rhs; a.u = sol; a.count = count;
         return a;
     }
@@ -466,16 +428,7 @@ struct StrSwzDev {
         HIPCK(hipMemsetAsync(piv, 0, sizeof(int) * npiv, g_ctx.stream));
         HIPCK(hipMemsetAsync(count, 0, sizeof(unsigned) * 4, g_ctx.stream));
         const StrSwzArgs a = args(nullptr, nullptr);
-        switch (P.nc) {
-            case 1: factor_nc<1>(a, nslots); break;
-            case 2: factor_nc<2>(a, nslots); break;
-            case 3: factor_nc<3>(a, nslots); break;
-            case 4: factor_nc<4>(a, nslots); break;
-            case 5: factor_nc<5>(a, nslots); break;
-            case 6: factor_nc<6>(a, nslots); break;
-            case 7: factor_nc<7>(a, nslots); break;
-            default: return ERROR_INPUT_PAR;
-        }
+        if (str_for_nc(P.nc, [&](auto NC) { factor_nc<NC()>(a, nslots); return 0; }) < 0) return ERROR_INPUT_PAR;
         return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
     }
     int counts()
@@ -495,8 +448,8 @@ struct StrSwzDev {
         for (size_t l = 0; l + 1 < P.lvl_first.size(); ++l) {
             const int first = P.lvl_first[l], cnt = P.lvl_first[l + 1] - first;
             const dim3 grid((unsigned)((cnt + VPW - 1) / VPW)), block(64);
-            if (M.form != STR_G && M.nb1 == 7) hipLaunchKernelGGL((k_str_swz_level<NC, 7, W>), grid, block, lds, g_ctx.stream, a, first, cnt);
-            else if (M.form != STR_G && M.nb1 == 5) hipLaunchKernelGGL((k_str_swz_level<NC, 5, W>), grid, block, lds, g_ctx.stream, a, first, cnt);
+            if (M.form != STR_G && M.nb == 7) hipLaunchKernelGGL((k_str_swz_level<NC, 7, W>), grid, block, lds, g_ctx.stream, a, first, cnt);
+            else if (M.form != STR_G && M.nb == 5) hipLaunchKernelGGL((k_str_swz_level<NC, 5, W>), grid, block, lds, g_ctx.stream, a, first, cnt);
             else hipLaunchKernelGGL((k_str_swz_level<NC, 0, W>), grid, block, lds, g_ctx.stream, a, first, cnt);
             ++launches;
         }
@@ -514,16 +467,7 @@ struct StrSwzDev {
         if (P.ngrid <= 0) return FASP_SUCCESS;
         const StrSwzArgs a = args(rhs, sol);
         launches = 0;
-        switch (P.nc) {
-            case 1: sweep_nc<1>(a); break;
-            case 2: sweep_nc<2>(a); break;
-            case 3: sweep_nc<3>(a); break;
-            case 4: sweep_nc<4>(a); break;
-            case 5: sweep_nc<5>(a); break;
-            case 6: sweep_nc<6>(a); break;
-            case 7: sweep_nc<7>(a); break;
-            default: return ERROR_INPUT_PAR;
-        }
+        if (str_for_nc(P.nc, [&](auto NC) { sweep_nc<NC()>(a); return 0; }) < 0) return ERROR_INPUT_PAR;
         return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
     }
     // z = 0, one sweep with b = r: fasp_precond_dstr_blockgs on device vectors
@@ -536,7 +480,7 @@ struct StrSwzDev {
     double bytes() const
     {
         double s = 0.0;
-        for (int i : P.list) { const double m = P.msize[(size_t)i]; s += 8.0 * m * m + 4.0 * m + 8.0 * m * ((double)M.nb1 * P.nc + 3.0) + 4.0 * (P.nneigh + 1); }
+        for (int i : P.list) { const double m = P.msize[(size_t)i]; s += 8.0 * m * m + 4.0 * m + 8.0 * m * ((double)M.nb * P.nc + 3.0) + 4.0 * (P.nneigh + 1); }
         return s;
     }
 };
