@@ -72,6 +72,9 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_hip_str_sweep", "fasp_hip_str_sweep_form", "fasp_hip_str_sweep_levels", "fasp_hip_time_str_sweep",
     "fasp_generate_diaginv_block", "fasp_smoother_dstr_swz", "fasp_precond_dstr_blockgs", "fasp_solver_dstr_krylov_blockgs",
     "fasp_hip_str_swz", "fasp_hip_str_swz_levels", "fasp_hip_time_str_swz",
+    "fasp_param_swz_init", "fasp_dcsr_sympart", "fasp_dcsr_shift", "fasp_sparse_mis", "fasp_swz_dcsr_setup", "fasp_dcsr_swz_forward",
+    "fasp_dcsr_swz_backward", "fasp_precond_swz", "fasp_swz_data_free", "fasp_solver_dcsr_krylov_swz",
+    "fasp_hip_csr_swz_levels", "fasp_hip_csr_swz", "fasp_hip_csr_swz_resident_count", "fasp_hip_time_csr_swz",
 ]
 
 
@@ -352,6 +355,30 @@ def lib():
     L.fasp_hip_str_swz.argtypes = [A_, I_, C.c_int, I_, D_, D_, C.c_int, I_]
     L.fasp_hip_str_swz_levels.argtypes = [A_, I_, C.c_int, I_, I_, I_, C.c_int]
     L.fasp_hip_time_str_swz.argtypes = [A_, I_, C.c_int, I_, C.c_int, D_, D_, I_]
+    # the CSR overlapping Schwarz method (BlaSchwarzSetup.c, PreCSR.c:371, PreDataInit.c:494, AuxParam.c:617, SolCSR.c:401)
+    SD_, SP_, M_ = P(T.SWZ_data), P(T.SWZ_param), P(T.dCSRmat)
+    L.fasp_param_swz_init.argtypes = [SP_]
+    L.fasp_param_swz_init.restype = None
+    L.fasp_dcsr_sympart.argtypes = [M_]
+    L.fasp_dcsr_sympart.restype = T.dCSRmat
+    L.fasp_dcsr_shift.argtypes = [M_, C.c_int]
+    L.fasp_dcsr_shift.restype = None
+    L.fasp_sparse_mis.argtypes = [M_]
+    L.fasp_sparse_mis.restype = T.ivector
+    L.fasp_swz_dcsr_setup.argtypes = [SD_, SP_]
+    L.fasp_dcsr_swz_forward.argtypes = [SD_, SP_, V_, V_]
+    L.fasp_dcsr_swz_forward.restype = None
+    L.fasp_dcsr_swz_backward.argtypes = [SD_, SP_, V_, V_]
+    L.fasp_dcsr_swz_backward.restype = None
+    L.fasp_precond_swz.argtypes = [T.c_double_p, T.c_double_p, C.c_void_p]
+    L.fasp_precond_swz.restype = None
+    L.fasp_swz_data_free.argtypes = [SD_]
+    L.fasp_swz_data_free.restype = None
+    L.fasp_solver_dcsr_krylov_swz.argtypes = [M_, V_, V_, P(T.ITS_param), SP_]
+    L.fasp_hip_csr_swz_levels.argtypes = [SD_, C.c_int, I_, C.c_int]
+    L.fasp_hip_csr_swz.argtypes = [SD_, C.c_int, D_, D_, C.c_int, I_, D_, I_]
+    L.fasp_hip_csr_swz_resident_count.argtypes = []
+    L.fasp_hip_time_csr_swz.argtypes = [SD_, C.c_int, D_, D_, I_]
     return L
 
 

@@ -214,3 +214,20 @@ class ILU_data(C.Structure):
                 ("nwork", C.c_int), ("work", c_double_p), ("iperm", c_int_p), ("ncolors", C.c_int),
                 ("ic", c_int_p), ("icmap", c_int_p), ("uptr", c_int_p), ("nlevL", C.c_int), ("nlevU", C.c_int),
                 ("ilevL", c_int_p), ("ilevU", c_int_p), ("jlevL", c_int_p), ("jlevU", c_int_p)]
+
+
+class SWZ_param(C.Structure):
+    """fasp.h:430: parameters of the Schwarz method (sizeof == 16)."""
+    _fields_ = [("print_level", C.c_short), ("SWZ_type", C.c_short), ("SWZ_maxlvl", C.c_int), ("SWZ_mmsize", C.c_int),
+                ("SWZ_blksolver", C.c_int)]
+
+
+class SWZ_data(C.Structure):
+    """fasp.h:724: the Schwarz blocks of a CSR matrix (A is 1-based); filled by fasp_swz_dcsr_setup, released by fasp_swz_data_free."""
+    _fields_ = [("A", dCSRmat), ("nblk", C.c_int), ("iblock", c_int_p), ("jblock", c_int_p), ("rhsloc", c_double_p),
+                ("rhsloc1", dvector), ("xloc1", dvector), ("au", c_double_p), ("al", c_double_p), ("SWZ_type", C.c_int),
+                ("blk_solver", C.c_int), ("memt", C.c_int), ("mask", c_int_p), ("maxbs", C.c_int), ("maxa", c_int_p),
+                ("blk_data", C.POINTER(dCSRmat)), ("mumps", C.c_void_p), ("swzparam", C.POINTER(SWZ_param))]
+
+
+SCHWARZ_FORWARD, SCHWARZ_BACKWARD, SCHWARZ_SYMMETRIC = 1, 2, 3

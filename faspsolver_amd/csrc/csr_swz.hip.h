@@ -1,0 +1,478 @@
+// csr_swz.hip.h -- the overlapping (multiplicative) Schwarz method of a CSR matrix on the device: block factorisation and sweeps.
+// Part of the single translation unit solver.hip (included there after str_common.hip.h; not a stand-alone header).
+//
+// Reference: fasp_dcsr_swz_forward / _backward (BlaSchwarzSetup.c:218 / :328), fasp_smat_lu_decomp (BlaSmallMatLU.c:52).  DESIGN.md section
+// 3.10.  The blocks are those of fasp_swz_dcsr_setup (csrc/csr_swz_setup.cpp): block v has the members jblock[iblock[v] .. iblock[v + 1]), m of
+// them, m <= 256.  A visit of block v computes rhs_i = b[k_i] - sum val x[k_j] over the entries of row k_i whose column is outside the block,
+// in the row's entry order, solves the block and assigns x[k_i] = u_i.  The reference build solves a block with GMRES to 1e-8 (or exactly,
+// with a direct solver compiled in); here every block is solved directly, by a dense LU with row interchanges:
+//   factor   the block's inside entries (blk_data[v]) are added into a zeroed m x m matrix in entry order; column k: the pivot is the first
+//            row j >= k of largest |a_jk|, the two whole rows change places, |a_kk| < 1e-20 stops the block (it is refused), otherwise
+//            a_ik = a_ik / a_kk and a_ij = a_ij - a_ik a_kj -- independent across (i, j), so lane-parallel without changing a bit;
+//   solve    the interchanges, L y = P rhs column by column (every row subtracts its terms with the column ascending), U u = y column by
+//            column from the last one down: u_c = y_c / a_cc, then y_r = y_r - u_c a_rc for r < c -- every row subtracts its terms with the
+//            column DESCENDING, then divides.  That order is a choice (no reference LU exists to match); it makes the back substitution
+//            as parallel as the forward one.  No fused multiply-add (-ffp-contract=off).
+//
+// Store: the factor of block v at fac_off[v] (64-bit; the blocks are packed at their own size, m^2 doubles), column by column -- entry (r, c)
+// at c m + r -- so that the lanes of a wavefront (lane = row) read consecutive doubles of one column; its pivots at iblock[v]; for every
+// local row its outside entries (global column, value) in entry order.
+//
+// Schedule: writes(v) = the members of block v, reads(v) = the outside columns of its rows; str_visit_levels over the sequence 0 .. nblk-1
+// (forward) and over nblk-1 .. 0 (backward), the blocks sorted stably by level, one launch per level over its slice of the list.
+// k_csr_swz_factor: one wavefront per block (a workgroup of 64), in LDS where m <= 64, else in place in the store.
+// k_csr_swz_level<R, LDSF>: one wavefront per block, up to four blocks per workgroup, lane = local rows lane + 64 q, q < R (maxbs <= 64 R);
+// R = 1 stages the factor in LDS (measured first: reading the store four columns per round trip, m / 4 dependent round trips each way,
+// 15.8 us per level at SWZ_maxlvl 2 on P7(64)).
+
+namespace fasp_str {
+
+constexpr int CSR_SWZ_MAX_BS = 256;
+
+struct CsrSwzArgs {
+    const int*       iblock;    // nblk + 1
+    const int*       jblock;    // the members (global rows, 0-based)
+    const long long* in_ptr;    // per member slot: its inside entries (local column, value), nmem + 1
+    const int*       in_col;
+    const double*    in_val;
+    const long long* out_ptr;   // per member slot: its outside entries (global column, value), nmem + 1
+    const int*       out_col;
+    const double*    out_val;
+    const long long* fac_off;   // nblk + 1
+    double*          fac;
+    int*             piv;       // per member slot
+    int*             flag;      // per block: 1 a row interchange, 2 stopped
+    const int*       list;      // the blocks of a direction sorted by level
+    const double*    b;
+    double*          x;
+};
+
+__global__ __launch_bounds__(64) void k_csr_swz_factor(const CsrSwzArgs a, int nblk)
+{
+    __shared__ double s_w[64 * 64];
+    const int v = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (v >= nblk) return;
+    const int p0 = a.iblock[v], m = a.iblock[v + 1] - p0, mm = m * m;
+    double* F = a.fac + a.fac_off[v];
+    double* W = m <= 64 ? s_w : F;
+    for (int e = lane; e < mm; e += 64) W[e] = 0.0;
+    __syncthreads();
+    for (int r = lane; r < m; r += 64)
+        for (long long e = a.in_ptr[p0 + r]; e < a.in_ptr[p0 + r + 1]; ++e) {
+            double* w = W + (size_t)a.in_col[e] * m + r;
+            *w = *w + a.in_val[e];
+        }
+    __syncthreads();
+    bool swapped = false, stopped = false;
+    for (int c = 0; c < m; ++c) {
+        // the first row of largest |a_rc|, r >= c: per lane over its rows ascending, then across the lanes (the smaller row wins a tie)
+        double bv = -1.0;
+        int    bi = 0x7fffffff;
+        for (int r = c + lane; r < m; r += 64) {
+            const double t = fabs(W[(size_t)c * m + r]);
+            if (bv < t) { bv = t; bi = r; }
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double ov = __shfl_xor(bv, off);
+            const int    oi = __shfl_xor(bi, off);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        const int pk = bi < m ? bi : c;   // (a column of NaN keeps its row, as the reference's comparison does)
+        if (lane == 0) a.piv[p0 + c] = pk;
+        if (pk != c) {
+            swapped = true;
+            for (int j = lane; j < m; j += 64) {
+                const double t = W[(size_t)j * m + c];
+                W[(size_t)j * m + c] = W[(size_t)j * m + pk];
+                W[(size_t)j * m + pk] = t;
+            }
+        }
+        __syncthreads();
+        const double d = W[(size_t)c * m + c];
+        if (fabs(d) < 1e-20) { stopped = true; break; }   // SMALLREAL
+        for (int r = c + 1 + lane; r < m; r += 64) W[(size_t)c * m + r] = W[(size_t)c * m + r] / d;
+        __syncthreads();
+        const int nr = m - c - 1;
+        for (int e = lane; e < nr * nr; e += 64) {
+            const int j = c + 1 + e / nr, r = c + 1 + e % nr;
+            W[(size_t)j * m + r] = W[(size_t)j * m + r] - W[(size_t)c * m + r] * W[(size_t)j * m + c];
+        }
+        __syncthreads();
+    }
+    if (W != F)
+        for (int e = lane; e < mm; e += 64) F[e] = W[e];
+    if (lane == 0) a.flag[v] = (swapped ? 1 : 0) | (stopped ? 2 : 0);
+}
+
+// y of row c (c >> 6 is the same in every lane) in every lane
+template <int R>
+__device__ __forceinline__ double swz_bcast(const double (&y)[R], int c)
+{
+    double s = y[0];
+#pragma unroll
+    for (int q = 1; q < R; ++q)
+        if ((c >> 6) == q) s = y[q];
+    // the lane is the same in the whole wavefront: two v_readlane instead of the LDS round trip of a shuffle (it sits on the dependent chain)
+    const long long bits = __double_as_longlong(s);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, c & 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(bits >> 32), c & 63);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// LDSF (R = 1 only): the factor of the wavefront's block is staged in LDS (dynamic: blockDim.x / 64 slots of ms^2 doubles, at most 64 KB), all
+// its loads in flight at once, the first sixteen per lane issued before the rhs is gathered; the substitutions then read LDS.  Otherwise
+// they read the store, four columns per round trip.  The workgroup's only barrier is the one after the staging; a wavefront beyond the
+// level's end takes part in it with an empty block.
+template <int R, bool LDSF>
+__global__ __launch_bounds__(256) void k_csr_swz_level(const CsrSwzArgs a, int first, int count, int ms)
+{
+    extern __shared__ double s_swz_fac[];
+    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, wpb = (int)blockDim.x >> 6;
+    const long long t = (long long)blockIdx.x * wpb + wv;
+    const bool live = t < count;
+    if (!LDSF && !live) return;   // (the whole wavefront; this form has no barrier)
+    const int v = a.list[first + (live ? (int)t : 0)];
+    const int p0 = a.iblock[v], m = live ? a.iblock[v + 1] - p0 : 0, mm = m * m;
+    const double* __restrict__ G = a.fac + a.fac_off[v];
+    double* sF = s_swz_fac + (size_t)wv * ms * ms;
+    double st0[16];
+    if (LDSF) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) st0[q] = lane + 64 * q < mm ? G[lane + 64 * q] : 0.0;
+    }
+    double y[R];
+    int    ki[R];
+    // rhs_i = b[k_i] - sum val x[k_j] over the outside entries of row k_i, in entry order
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const int r = lane + 64 * q;
+        y[q] = 0.0; ki[q] = -1;
+        if (r < m) {
+            const int k = a.jblock[p0 + r];
+            ki[q] = k;
+            double s = a.b[k];
+            for (long long e = a.out_ptr[p0 + r]; e < a.out_ptr[p0 + r + 1]; ++e) s = s - a.out_val[e] * a.x[a.out_col[e]];
+            y[q] = s;
+        }
+    }
+    // the interchanges rhs[k] <-> rhs[pivot[k]], k ascending (pivot[k] >= k: they can all be applied before the substitution): the row
+    // that ends up at row r is found by walking the pivots backwards
+    if (a.flag[v] & 1) {
+        int src[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) src[q] = lane + 64 * q;
+        for (int c = m - 1; c >= 0; --c) {
+            const int pk = a.piv[p0 + c];
+#pragma unroll
+            for (int q = 0; q < R; ++q) src[q] = src[q] == c ? pk : src[q] == pk ? c : src[q];
+        }
+        double z[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            z[q] = y[q];
+#pragma unroll
+            for (int q2 = 0; q2 < R; ++q2) {
+                const double g = __shfl(y[q2], src[q] & 63);
+                if ((src[q] >> 6) == q2) z[q] = g;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < R; ++q) y[q] = z[q];
+    }
+    if (LDSF) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (lane + 64 * q < mm) sF[lane + 64 * q] = st0[q];
+        for (int e0 = 1024 + lane; e0 < mm; e0 += 64 * 8) {
+            double tmp[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) tmp[q] = e0 + 64 * q < mm ? G[e0 + 64 * q] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (e0 + 64 * q < mm) sF[e0 + 64 * q] = tmp[q];
+        }
+        __syncthreads();
+    }
+    const double* F = LDSF ? sF : G;
+    // L y = P rhs, four columns at a time: their loads do not depend on y and are issued ahead of the chain
+    for (int c0 = 0; c0 + 1 < m; c0 += 4) {
+        double l[4][R];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int c = c0 + u, r = lane + 64 * q;
+                l[u][q] = (r > c && r < m) ? F[(size_t)c * m + r] : 0.0;
+            }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + u;
+            if (c + 1 < m) {
+                const double yc = swz_bcast<R>(y, c);
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    const int r = lane + 64 * q;
+                    if (r > c && r < m) y[q] = y[q] - yc * l[u][q];
+                }
+            }
+        }
+    }
+    // U u = y from the last column down: u_c = y_c / a_cc, then every row above subtracts u_c a_rc
+    for (int c0 = m - 1; c0 >= 0; c0 -= 4) {
+        double uu[4][R], dg[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 - u;
+            dg[u] = c >= 0 ? F[(size_t)c * m + c] : 1.0;
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int r = lane + 64 * q;
+                uu[u][q] = (c >= 0 && r < c) ? F[(size_t)c * m + r] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 - u;
+            if (c >= 0) {
+                const double xc = swz_bcast<R>(y, c) / dg[u];
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    const int r = lane + 64 * q;
+                    if (r == c) y[q] = xc;
+                    else if (r < c) y[q] = y[q] - xc * uu[u][q];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+        if (ki[q] >= 0) a.x[ki[q]] = y[q];
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+// everything the host decides before a device is touched: the checked blocks, the entries of every member row split into inside (blk_data)
+// and outside the block, the offsets of the factor store, the levels of both directions
+struct CsrSwzPlan {
+    int n = 0, nblk = 0, nmem = 0, maxbs = 0, nnz = 0;
+    std::vector<long long> in_ptr, out_ptr, fac_off;
+    std::vector<int>       in_col, out_col;
+    std::vector<double>    in_val, out_val;
+    std::vector<int>       lev[2], list[2], lvl_first[2];   // [0] forward, [1] backward; lev by position in the direction's sequence
+    int levels[2] = {0, 0};
+};
+
+// Fills P from an SWZ_data that fasp_swz_dcsr_setup has filled; refusals are reported under fn.  Pure host code.
+static int csr_swz_plan(const char* fn, const SWZ_data* d, CsrSwzPlan& P)
+{
+    auto bad = [&](const char* why) { std::fprintf(stderr, "### ERROR: %s: %s\n", fn, why); return ERROR_INPUT_PAR; };
+    if (!d) return bad("NULL SWZ_data");
+    const dCSRmat& A = d->A;
+    const int n = A.row;
+    if (A.row != A.col || n <= 0 || A.nnz < 0 || !A.IA || (A.nnz > 0 && (!A.JA || !A.val))) return bad("SWZ_data.A is not a square matrix");
+    if (A.IA[0] != 1 || A.IA[n] != A.nnz + 1) return bad("SWZ_data.A is not 1-based");
+    for (int i = 0; i < n; ++i) if (A.IA[i + 1] < A.IA[i]) return bad("SWZ_data.A.IA decreases");
+    for (int k = 0; k < A.nnz; ++k) if (A.JA[k] < 1 || A.JA[k] > n) return bad("a column of SWZ_data.A is outside 1 .. n");
+    const int nblk = d->nblk;
+    if (nblk <= 0 || !d->iblock || !d->jblock || !d->blk_data || d->iblock[0] != 0) return bad("SWZ_data holds no blocks (fasp_swz_dcsr_setup first)");
+    if (d->maxbs > CSR_SWZ_MAX_BS) return bad("a block has more than 256 rows");
+    for (int v = 0; v < nblk; ++v) {
+        const int m = d->iblock[v + 1] - d->iblock[v];
+        if (m < 1 || m > d->maxbs) return bad("the size of a block is outside 1 .. maxbs");
+    }
+    const int nmem = d->iblock[nblk];
+    P.n = n; P.nblk = nblk; P.nmem = nmem; P.maxbs = d->maxbs; P.nnz = A.nnz;
+    P.in_ptr.assign((size_t)nmem + 1, 0); P.out_ptr.assign((size_t)nmem + 1, 0); P.fac_off.assign((size_t)nblk + 1, 0);
+    std::vector<int> mask((size_t)n, 0);
+    for (int v = 0; v < nblk; ++v) {
+        const int p0 = d->iblock[v], m = d->iblock[v + 1] - p0;
+        const dCSRmat& B = d->blk_data[v];
+        P.fac_off[(size_t)v + 1] = P.fac_off[(size_t)v] + (long long)m * m;
+        if (B.row != m || !B.IA || B.IA[0] != 0 || B.IA[m] < 0 || (B.IA[m] > 0 && (!B.JA || !B.val))) return bad("blk_data does not fit its block");
+        for (int i = 0; i < m; ++i) {
+            const int k = d->jblock[p0 + i];
+            if (k < 0 || k >= n || mask[(size_t)k]) return bad("a member of a block is outside 0 .. n-1 or named twice");
+            mask[(size_t)k] = 1;
+        }
+        for (int i = 0; i < m; ++i) {
+            if (B.IA[i + 1] < B.IA[i] || B.IA[i + 1] > B.IA[m]) return bad("blk_data does not fit its block");
+            for (int e = B.IA[i]; e < B.IA[i + 1]; ++e) {
+                if (B.JA[e] < 0 || B.JA[e] >= m) return bad("a column of blk_data is outside its block");
+                P.in_col.push_back(B.JA[e]); P.in_val.push_back(B.val[e]);
+            }
+            P.in_ptr[(size_t)p0 + i + 1] = (long long)P.in_col.size();
+            const int k = d->jblock[p0 + i];
+            for (int e = A.IA[k] - 1; e < A.IA[k + 1] - 1; ++e)
+                if (!mask[(size_t)A.JA[e] - 1]) { P.out_col.push_back(A.JA[e] - 1); P.out_val.push_back(A.val[e]); }
+            P.out_ptr[(size_t)p0 + i + 1] = (long long)P.out_col.size();
+        }
+        for (int i = 0; i < m; ++i) mask[(size_t)d->jblock[p0 + i]] = 0;
+    }
+    for (int dir = 0; dir < 2; ++dir) {
+        std::vector<int> seq((size_t)nblk);
+        for (int s = 0; s < nblk; ++s) seq[(size_t)s] = dir ? nblk - 1 - s : s;
+        auto writes = [&](size_t s, auto&& f) {
+            const int v = seq[s];
+            for (int p = d->iblock[v]; p < d->iblock[v + 1]; ++p) f(d->jblock[p]);
+        };
+        auto reads = [&](size_t s, auto&& f) {
+            const int v = seq[s];
+            for (long long e = P.out_ptr[(size_t)d->iblock[v]]; e < P.out_ptr[(size_t)d->iblock[v + 1]]; ++e) f(P.out_col[(size_t)e]);
+        };
+        P.levels[dir] = str_visit_levels(n, (size_t)nblk, writes, reads, P.lev[dir]);
+        str_bucket_by_level(seq, P.lev[dir], P.levels[dir], P.lvl_first[dir], P.list[dir], nullptr);
+    }
+    return FASP_SUCCESS;
+}
+
+// the blocks of an SWZ_data resident on the device: members, entries, factors, pivots, both level lists; built once, applied many times
+struct CsrSwzDev {
+    int n = 0, nblk = 0, nmem = 0, maxbs = 0, nnz = 0;
+    std::vector<int> lvl_first[2];
+    int        levels[2] = {0, 0};
+    int       *iblock = nullptr, *jblock = nullptr, *in_col = nullptr, *out_col = nullptr, *piv = nullptr, *flag = nullptr, *list[2] = {nullptr, nullptr};
+    long long *in_ptr = nullptr, *out_ptr = nullptr, *fac_off = nullptr;
+    double    *in_val = nullptr, *out_val = nullptr, *fac = nullptr, *b = nullptr, *x = nullptr;
+    size_t     nfac = 0;
+    double     sweep_bytes = 0.0;
+    DevPool    pool;
+    bool       ok = false;
+    int        st = ERROR_ALLOC_MEM;   // why not ok
+    int        nswap = 0, nstopped = 0, first_stopped = -1, launches = 0, nfactor = 0;
+
+    CsrSwzDev(const SWZ_data* d, const CsrSwzPlan& P) : n(P.n), nblk(P.nblk), nmem(P.nmem), maxbs(P.maxbs), nnz(P.nnz)
+    {
+        for (int dir = 0; dir < 2; ++dir) { lvl_first[dir] = P.lvl_first[dir]; levels[dir] = P.levels[dir]; }
+        nfac = (size_t)P.fac_off[(size_t)nblk];
+        const size_t nin = P.in_col.size(), nout = P.out_col.size();
+        const double need = 8.0 * (double)nfac + 12.0 * (double)(nin + nout) + 24.0 * ((double)nmem + nblk + 2) + 4.0 * (2.0 * nmem + 4.0 * nblk + 1) + 16.0 * n;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); st = ERROR_MISC; return; }
+        if (need > (double)free_b) return;   // ERROR_ALLOC_MEM
+        sweep_bytes = 8.0 * (double)nfac + 36.0 * (double)nmem + 20.0 * (double)nout + 24.0 * nblk;
+        if (!pool.get(&iblock, (size_t)nblk + 1) || !pool.get(&jblock, (size_t)nmem) || !pool.get(&in_ptr, (size_t)nmem + 1) || !pool.get(&in_col, nin) ||
+            !pool.get(&in_val, nin) || !pool.get(&out_ptr, (size_t)nmem + 1) || !pool.get(&out_col, nout) || !pool.get(&out_val, nout) ||
+            !pool.get(&fac_off, (size_t)nblk + 1) || !pool.get(&fac, nfac) || !pool.get(&piv, (size_t)nmem) || !pool.get(&flag, (size_t)nblk) ||
+            !pool.get(&list[0], (size_t)nblk) || !pool.get(&list[1], (size_t)nblk) || !pool.get(&b, (size_t)n) || !pool.get(&x, (size_t)n))
+            return;
+        auto up = [](void* dst, const void* src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+        st = ERROR_MISC;
+        if (!up(iblock, d->iblock, sizeof(int) * ((size_t)nblk + 1)) || !up(jblock, d->jblock, sizeof(int) * (size_t)nmem) ||
+            !up(in_ptr, P.in_ptr.data(), sizeof(long long) * ((size_t)nmem + 1)) || !up(in_col, P.in_col.data(), sizeof(int) * nin) ||
+            !up(in_val, P.in_val.data(), sizeof(double) * nin) || !up(out_ptr, P.out_ptr.data(), sizeof(long long) * ((size_t)nmem + 1)) ||
+            !up(out_col, P.out_col.data(), sizeof(int) * nout) || !up(out_val, P.out_val.data(), sizeof(double) * nout) ||
+            !up(fac_off, P.fac_off.data(), sizeof(long long) * ((size_t)nblk + 1)) || !up(list[0], P.list[0].data(), sizeof(int) * (size_t)nblk) ||
+            !up(list[1], P.list[1].data(), sizeof(int) * (size_t)nblk))
+            return;
+        if (factor() < 0) return;
+        ok = true; st = FASP_SUCCESS;
+    }
+
+    CsrSwzArgs args(int dir, const double* rhs, double* sol) const
+    {
+        CsrSwzArgs a{};
+        a.iblock = iblock; a.jblock = jblock; a.in_ptr = in_ptr; a.in_col = in_col; a.in_val = in_val; a.out_ptr = out_ptr; a.out_col = out_col;
+        a.out_val = out_val; a.fac_off = fac_off; a.fac = fac; a.piv = piv; a.flag = flag; a.list = list[dir]; a.b = rhs; a.x = sol;
+        return a;
+    }
+    // factor every block on the device (asynchronous)
+    int launch_factor()
+    {
+        HIPCK(hipMemsetAsync(piv, 0, sizeof(int) * (size_t)nmem, g_ctx.stream));
+        HIPCK(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)nblk, g_ctx.stream));
+        hipLaunchKernelGGL(k_csr_swz_factor, dim3((unsigned)nblk), dim3(64), 0, g_ctx.stream, args(0, nullptr, nullptr), nblk);
+        return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
+    }
+    int factor()
+    {
+        const int s = launch_factor();
+        if (s < 0) return s;
+        std::vector<int> hf((size_t)nblk);
+        HIPCK(hipStreamSynchronize(g_ctx.stream));
+        HIPCK(hipMemcpy(hf.data(), flag, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost));
+        nswap = nstopped = 0; first_stopped = -1;
+        for (int v = 0; v < nblk; ++v) {
+            nswap += hf[(size_t)v] & 1;
+            if (hf[(size_t)v] & 2) { if (!nstopped) first_stopped = v; ++nstopped; }
+        }
+        ++nfactor;
+        return FASP_SUCCESS;
+    }
+    template <int R> void sweep_r(const CsrSwzArgs& a, int dir)
+    {
+        for (size_t l = 0; l + 1 < lvl_first[dir].size(); ++l) {
+            const int first = lvl_first[dir][l], cnt = lvl_first[dir][l + 1] - first;
+            if (R == 1) {   // the factors in LDS: as many wavefronts per workgroup as 64 KB hold, four at most
+                const int wpb = maxbs * maxbs * 8 * 4 <= 65536 ? 4 : 2;
+                hipLaunchKernelGGL((k_csr_swz_level<R, R == 1>), dim3((unsigned)((cnt + wpb - 1) / wpb)), dim3(64 * wpb), sizeof(double) * (size_t)maxbs * maxbs * wpb,
+                                   g_ctx.stream, a, first, cnt, maxbs);
+            } else
+                hipLaunchKernelGGL((k_csr_swz_level<R, false>), dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, g_ctx.stream, a, first, cnt, maxbs);
+            ++launches;
+        }
+    }
+    // one sweep on device vectors, in place in sol; dir 0 forward, 1 backward
+    int sweep(int dir, const double* rhs, double* sol)
+    {
+        const CsrSwzArgs a = args(dir, rhs, sol);
+        if (maxbs <= 64) sweep_r<1>(a, dir);
+        else if (maxbs <= 128) sweep_r<2>(a, dir);
+        else sweep_r<4>(a, dir);
+        return hipGetLastError() == hipSuccess ? FASP_SUCCESS : ERROR_MISC;
+    }
+    // the sweeps of fasp_precond_swz for an SWZ_type, from what sol holds
+    int sweeps_of_type(int type, const double* rhs, double* sol)
+    {
+        if (type == 2) return sweep(1, rhs, sol);
+        const int s = sweep(0, rhs, sol);
+        return (s < 0 || type != 3) ? s : sweep(1, rhs, sol);
+    }
+    // z = 0, b = r, the sweeps of the type: fasp_precond_swz on device vectors
+    int precond(int type, const double* r, double* z)
+    {
+        HIPCK(hipMemsetAsync(z, 0, sizeof(double) * (size_t)n, g_ctx.stream));
+        return sweeps_of_type(type, r, z);
+    }
+};
+
+// the device copies, found through the address of the SWZ_data they stand for (made at its first sweep, dropped by fasp_swz_data_free)
+static std::vector<std::pair<const SWZ_data*, CsrSwzDev*>> g_csr_swz_resident;
+
+static void csr_swz_drop(const SWZ_data* d)
+{
+    for (size_t q = 0; q < g_csr_swz_resident.size(); ++q)
+        if (g_csr_swz_resident[q].first == d) {
+            delete g_csr_swz_resident[q].second;
+            g_csr_swz_resident.erase(g_csr_swz_resident.begin() + (long)q);
+            return;
+        }
+}
+
+// The resident copy of d, made now if there is none or if the cheap invariants no longer hold.  nullptr: *st says why (refused data, no
+// device, no memory).  A copy with stopped blocks is handed out: the caller refuses it (csr_swz_refuse_stopped).
+static CsrSwzDev* csr_swz_device_of(const char* fn, const SWZ_data* d, int* st)
+{
+    *st = FASP_SUCCESS;
+    if (!d) { *st = ERROR_INPUT_PAR; return nullptr; }
+    for (const auto& e : g_csr_swz_resident)
+        if (e.first == d) {
+            const CsrSwzDev* M = e.second;
+            if (d->iblock && d->nblk == M->nblk && d->maxbs == M->maxbs && d->iblock[M->nblk] == M->nmem && d->A.nnz == M->nnz && d->A.row == M->n) return e.second;
+            csr_swz_drop(d);
+            break;
+        }
+    CsrSwzPlan P;
+    if ((*st = csr_swz_plan(fn, d, P)) < 0) return nullptr;
+    if (ctx_init() < 0) { *st = ERROR_MISC; return nullptr; }
+    CsrSwzDev* M = new CsrSwzDev(d, P);
+    if (!M->ok) { *st = M->st; delete M; return nullptr; }
+    g_csr_swz_resident.emplace_back(d, M);
+    return M;
+}
+
+static int csr_swz_refuse_stopped(const char* fn, const CsrSwzDev& M)
+{
+    if (!M.nstopped) return FASP_SUCCESS;
+    std::fprintf(stderr, "### ERROR: %s: the factorisation of %d block(s) stopped at a pivot below 1e-20 (the first: block %d)\n", fn, M.nstopped, M.first_stopped);
+    return ERROR_INPUT_PAR;
+}
+}  // namespace fasp_str

@@ -1,0 +1,198 @@
+// csr_swz_api.hip.h -- the CSR overlapping Schwarz entry points of the C ABI: BlaSchwarzSetup.c:218 / :328, PreCSR.c:371, PreDataInit.c:494,
+// SolCSR.c:401 and the dev entries of fasp_hip_dev.h (csrc/csr_swz.hip.h).
+// Part of the single translation unit solver.hip (included there inside extern "C"; not a stand-alone header).
+
+namespace {
+[[noreturn]] void csr_swz_fail(const char* fn, int st)
+{
+    if (st == ERROR_MISC && !g_ctx.ready) die_no_device(fn);
+    std::fprintf(stderr, "### ERROR: %s: failed (%d)\n", fn, st);
+    std::exit(st);
+}
+// the resident copy of d, or the end of the process as the void entries of the reference's interface have no way to report
+CsrSwzDev* csr_swz_need(const char* fn, const SWZ_data* d)
+{
+    int st;
+    CsrSwzDev* M = csr_swz_device_of(fn, d, &st);
+    if (!M) csr_swz_fail(fn, st);
+    if (csr_swz_refuse_stopped(fn, *M) < 0) std::exit(ERROR_INPUT_PAR);
+    return M;
+}
+// the sweeps of `type` (0: one forward sweep, 1: one backward sweep as dir; >= 2: by SWZ_type) with M on host vectors; zero_x: from x = 0
+int csr_swz_oneshot(CsrSwzDev& M, int dir, int type, const double* b, double* x, bool zero_x)
+{
+    const size_t n = (size_t)M.n;
+    HIPCK(hipMemcpyAsync(M.b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+    if (zero_x) HIPCK(hipMemsetAsync(M.x, 0, sizeof(double) * n, g_ctx.stream));
+    else HIPCK(hipMemcpyAsync(M.x, x, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+    const int st = dir >= 0 ? M.sweep(dir, M.b, M.x) : M.sweeps_of_type(type, M.b, M.x);
+    HIPCK(hipStreamSynchronize(g_ctx.stream));
+    if (st < 0) return st;
+    HIPCK(hipMemcpy(x, M.x, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return FASP_SUCCESS;
+}
+void csr_swz_sweep_entry(const char* fn, int dir, SWZ_data* d, dvector* x, dvector* b)
+{
+    if (!d || !x || !b || !x->val || !b->val) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", fn); return; }
+    if (x->row < d->A.row || b->row < d->A.row) { std::fprintf(stderr, "### ERROR: %s: x and b need %d entries\n", fn, d->A.row); return; }
+    CsrSwzDev* M = csr_swz_need(fn, d);
+    const int st = csr_swz_oneshot(*M, dir, 0, b->val, x->val, false);
+    if (st < 0) csr_swz_fail(fn, st);
+}
+void csr_swz_info(const CsrSwzDev& M, int launches, int* info)
+{
+    if (!info) return;
+    info[0] = M.levels[0]; info[1] = M.levels[1]; info[2] = launches; info[3] = M.nblk; info[4] = M.maxbs; info[5] = M.nswap;
+    info[6] = M.nstopped; info[7] = M.nfactor;
+}
+}  // namespace
+
+void fasp_dcsr_swz_forward(SWZ_data* swzdata, SWZ_param*, dvector* x, dvector* b)   // BlaSchwarzSetup.c:218
+{
+    FASP_ENTRY();
+    csr_swz_sweep_entry(__func__, 0, swzdata, x, b);
+}
+void fasp_dcsr_swz_backward(SWZ_data* swzdata, SWZ_param*, dvector* x, dvector* b)  // BlaSchwarzSetup.c:328
+{
+    FASP_ENTRY();
+    csr_swz_sweep_entry(__func__, 1, swzdata, x, b);
+}
+
+// PreCSR.c:371 on host vectors (a foreign Krylov method; this library's own bind it on the device, bind_swz_csr)
+void fasp_precond_swz(double* r, double* z, void* data)
+{
+    FASP_ENTRY();
+    SWZ_data* d = static_cast<SWZ_data*>(data);
+    if (!r || !z || !d) { std::fprintf(stderr, "### ERROR: %s: NULL argument\n", __func__); return; }
+    CsrSwzDev* M = csr_swz_need(__func__, d);
+    const int st = csr_swz_oneshot(*M, -1, d->SWZ_type, r, z, true);
+    if (st < 0) csr_swz_fail(__func__, st);
+}
+
+// PreDataInit.c:494, field by field; the device copy goes first
+void fasp_swz_data_free(SWZ_data* swzdata)
+{
+    FASP_ENTRY();
+    if (!swzdata) return;
+    csr_swz_drop(swzdata);
+    fasp_dcsr_free(&swzdata->A);
+    if (swzdata->blk_data) {
+        for (int i = 0; i < swzdata->nblk; ++i) fasp_dcsr_free(&swzdata->blk_data[i]);
+        std::free(swzdata->blk_data); swzdata->blk_data = nullptr;
+    }
+    swzdata->nblk = 0;
+    std::free(swzdata->iblock); swzdata->iblock = nullptr;
+    std::free(swzdata->jblock); swzdata->jblock = nullptr;
+    fasp_dvec_free(&swzdata->rhsloc1);
+    fasp_dvec_free(&swzdata->xloc1);
+    swzdata->memt = 0;
+    std::free(swzdata->mask); swzdata->mask = nullptr;
+    std::free(swzdata->maxa); swzdata->maxa = nullptr;
+}
+
+// SolCSR.c:401
+int fasp_solver_dcsr_krylov_swz(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, SWZ_param* schparam)
+{
+    FASP_ENTRY();
+    if (!A || !b || !x || !itparam || !schparam) return ERROR_INPUT_PAR;
+    if (A->row != A->col) { std::printf("### ERROR: %s: the matrix is %d x %d, not square\n", __func__, A->row, A->col); return ERROR_INPUT_PAR; }
+    if (schparam->SWZ_maxlvl < 0) { std::printf("### ERROR: %s: SWZ_maxlvl = %d is negative\n", __func__, schparam->SWZ_maxlvl); return ERROR_INPUT_PAR; }
+    SWZ_param swzparam;
+    swzparam.print_level   = 0;
+    swzparam.SWZ_mmsize    = schparam->SWZ_mmsize;
+    swzparam.SWZ_maxlvl    = schparam->SWZ_maxlvl;
+    swzparam.SWZ_type      = schparam->SWZ_type;
+    swzparam.SWZ_blksolver = schparam->SWZ_blksolver;
+    const short prtlvl = itparam->print_level;
+    const double t0 = wall_seconds();
+    SWZ_data D;
+    std::memset(&D, 0, sizeof(D));
+    D.A = fasp_dcsr_sympart(A);
+    fasp_dcsr_shift(&D.A, 1);
+    int status = fasp_swz_dcsr_setup(&D, &swzparam);   // a refusal: before any device work
+    if (status >= 0 && ctx_init() < 0) {
+        std::fprintf(stderr, "### ERROR: %s: no usable HIP device and no CPU fallback in libfasp_hip\n", __func__);
+        status = ERROR_MISC;
+    }
+    if (status >= 0) {
+        CsrSwzDev* M = csr_swz_device_of(__func__, &D, &status);   // upload and factor: part of the setup, as the reference's direct solvers are
+        if (M && csr_swz_refuse_stopped(__func__, *M) < 0) status = ERROR_INPUT_PAR;
+    }
+    if (status >= 0) {
+        std::printf("SWZ_Krylov method setup %f seconds.\n", wall_seconds() - t0);
+        precond prec{&D, fasp_precond_swz};
+        status = fasp_solver_dcsr_itsolver(A, b, x, &prec, itparam);
+        if (prtlvl > PRINT_NONE) std::printf("SWZ_Krylov method totally costs %.4f seconds.\n", wall_seconds() - t0);
+    }
+    fasp_swz_data_free(&D);
+    return status;
+}
+
+// ---- the dev entries (fasp_hip_dev.h) ------------------------------------------------------------------------------------------------
+int fasp_hip_csr_swz_levels(const SWZ_data* swz, int backward, int* level, int cap)
+{
+    FASP_ENTRY();
+    CsrSwzPlan P;
+    if (csr_swz_plan(__func__, swz, P) < 0) return ERROR_INPUT_PAR;
+    const int dir = backward ? 1 : 0;
+    for (int v = 0; v < P.nblk && v < cap && level; ++v) level[v] = P.lev[dir][(size_t)(dir ? P.nblk - 1 - v : v)];
+    return P.levels[dir];
+}
+
+int fasp_hip_csr_swz(SWZ_data* swz, int dir, const double* b, double* x, int nsweeps, int* info, double* fac, int* piv)
+{
+    FASP_ENTRY();
+    if (info) std::fill(info, info + 8, 0);
+    if (!swz || !b || !x || nsweeps < 0 || dir < 1 || dir > 3) return ERROR_INPUT_PAR;
+    int st;
+    CsrSwzDev* M = csr_swz_device_of(__func__, swz, &st);
+    if (!M) return st;
+    csr_swz_info(*M, 0, info);
+    if (fac) HIPCK(hipMemcpy(fac, M->fac, sizeof(double) * M->nfac, hipMemcpyDeviceToHost));
+    if (piv) HIPCK(hipMemcpy(piv, M->piv, sizeof(int) * (size_t)M->nmem, hipMemcpyDeviceToHost));
+    if (csr_swz_refuse_stopped(__func__, *M) < 0) return ERROR_INPUT_PAR;
+    const size_t n = (size_t)M->n;
+    HIPCK(hipMemcpy(M->b, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(M->x, x, sizeof(double) * n, hipMemcpyHostToDevice));
+    M->launches = 0;
+    for (int s = 0; s < nsweeps && st >= 0; ++s) st = M->sweeps_of_type(dir, M->b, M->x);
+    HIPCK(hipStreamSynchronize(g_ctx.stream));
+    if (st < 0) return st;
+    HIPCK(hipMemcpy(x, M->x, sizeof(double) * n, hipMemcpyDeviceToHost));
+    csr_swz_info(*M, M->launches, info);
+    return FASP_SUCCESS;
+}
+
+int fasp_hip_csr_swz_resident_count(void)
+{
+    FASP_ENTRY();
+    return (int)g_csr_swz_resident.size();
+}
+
+int fasp_hip_time_csr_swz(SWZ_data* swz, int reps, double* ms, double* bytes, int* info)
+{
+    FASP_ENTRY();
+    if (info) std::fill(info, info + 8, 0);
+    if (!swz || reps <= 0) return ERROR_INPUT_PAR;
+    int st;
+    CsrSwzDev* M = csr_swz_device_of(__func__, swz, &st);   // (the warm-up factorisation)
+    if (!M) return st;
+    csr_swz_info(*M, 0, info);
+    if (csr_swz_refuse_stopped(__func__, *M) < 0) return ERROR_INPUT_PAR;
+    const size_t n = (size_t)M->n;
+    std::vector<double> hb(n);
+    for (size_t i = 0; i < n; ++i) hb[i] = std::sin(0.37 * (double)i) + 0.1;
+    HIPCK(hipMemcpy(M->b, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCK(hipMemset(M->x, 0, sizeof(double) * n));
+    double t[3] = {0.0, 0.0, 0.0};
+    st = time_reps(reps, [&] { return M->launch_factor(); }, &t[0]);
+    for (int dir = 0; dir < 2 && st >= 0; ++dir) {
+        st = M->sweep(dir, M->b, M->x);   // warm-up
+        M->launches = 0;
+        if (st >= 0) st = time_reps(reps, [&] { return M->sweep(dir, M->b, M->x); }, &t[1 + dir]);
+    }
+    csr_swz_info(*M, M->launches / reps, info);
+    if (ms) { ms[0] = t[0]; ms[1] = t[1]; ms[2] = t[2]; }
+    if (bytes) { bytes[0] = 8.0 * (double)M->nfac; bytes[1] = M->sweep_bytes; }
+    return st;
+}

@@ -1,0 +1,257 @@
+// csr_swz_setup.cpp -- the host side of the overlapping Schwarz method of a CSR matrix: the parameter defaults (AuxParam.c:617), the symmetrised
+// pattern (BlaSparseCSR.c:1357 through BlaSparseCSR.c:952 and BlaSpmvCSR.c:60), the index shift (BlaSparseCSR.c:1212), the greedy independent set
+// (BlaSparseUtil.c:907) and the block setup (BlaSchwarzSetup.c:46 with its SWZ_level and SWZ_block).  Pure host code: no GPU needed.
+//
+// Every array comes out as the reference leaves it, entry order included: the blocks are integers and are exact.  What the reference leaves
+// uninitialised in SWZ_data (mumps, au, al, rhsloc, memt, blk_solver) is zeroed.  All memory is calloc'ed so that fasp_swz_data_free
+// (csrc/csr_swz.hip.h) releases it field by field.  The device sweeps serve blocks of at most 256 rows; a larger one is refused here.
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "fasp_internal.h"
+
+namespace {
+constexpr int CSR_SWZ_MAX_BS = 256;   // rows of a block at most (k_csr_swz_level<4>: four rows per lane)
+
+// a refusal's reason on stdout, where the reference's messages go, at once
+void say(const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    std::vprintf(fmt, ap);
+    va_end(ap);
+    std::fflush(stdout);
+}
+
+template <class T> T* zalloc(size_t count) { return static_cast<T*>(std::calloc(std::max<size_t>(count, 1), sizeof(T))); }
+
+// fasp_dcsr_trans (BlaSparseCSR.c:952): row j of AT holds the rows of A with an entry in column j, in the order of a scan of A
+void csr_transpose(const dCSRmat* A, std::vector<int>& tia, std::vector<int>& tja, std::vector<double>& tval)
+{
+    const int n = A->row, m = A->col, nnz = A->nnz;
+    tia.assign((size_t)m + 2, 0); tja.assign((size_t)std::max(nnz, 1), 0); tval.assign((size_t)std::max(nnz, 1), 0.0);
+    for (int j = 0; j < nnz; ++j) ++tia[(size_t)A->JA[j] + 2];
+    for (int i = 2; i <= m + 1; ++i) tia[(size_t)i] += tia[(size_t)i - 1];
+    for (int i = 0; i < n; ++i)
+        for (int p = A->IA[i]; p < A->IA[i + 1]; ++p) {
+            const int k = tia[(size_t)A->JA[p] + 1]++;
+            tja[(size_t)k] = i; tval[(size_t)k] = A->val[p];
+        }
+    tia.pop_back();   // tia[j] .. tia[j + 1]: row j
+}
+
+// SWZ_level (BlaSchwarzSetup.c:445) on the 1-based matrix: the breadth-first ball of `maxlev` levels around inroot in visiting order in jb,
+// maxa[l] the start of level l, maxa[*nlvl] the size; mask comes back all zero.  A root whose row has at most one entry is a block of one.
+void swz_level(int inroot, const dCSRmat* A, int* mask, int* nlvl, int* maxa, int* jb, int maxlev)
+{
+    const int *ia = A->IA, *ja = A->JA;
+    int lvl = 0;
+    if (ia[inroot + 1] - ia[inroot] <= 1) {
+        maxa[0] = 0; jb[0] = inroot; lvl = 1; maxa[1] = 1;
+    } else {
+        jb[0] = inroot;
+        int lvlend = 0, nsize = 1, lvsize = A->nnz;
+        mask[inroot] = 1;
+        while (lvsize > 0 && lvl < maxlev) {
+            const int lbegin = lvlend;
+            lvlend = nsize;
+            maxa[lvl] = lbegin;
+            ++lvl;
+            for (int i = lbegin; i < lvlend; ++i) {
+                const int node = jb[i];
+                for (int j = ia[node] - 1; j < ia[node + 1] - 1; ++j) {
+                    const int nbr = ja[j] - 1;
+                    if (mask[nbr] == 0) { jb[nsize++] = nbr; mask[nbr] = lvl; }
+                }
+            }
+            lvsize = nsize - lvlend;
+        }
+        maxa[lvl] = nsize;
+        for (int i = 0; i < nsize; ++i) mask[jb[i]] = 0;
+    }
+    *nlvl = lvl;
+}
+}  // namespace
+
+extern "C" {
+
+void fasp_param_swz_init(SWZ_param* swzparam)   // AuxParam.c:617
+{
+    if (!swzparam) return;
+    swzparam->print_level   = PRINT_NONE;
+    swzparam->SWZ_type      = 3;
+    swzparam->SWZ_maxlvl    = 2;
+    swzparam->SWZ_mmsize    = 200;
+    swzparam->SWZ_blksolver = 0;
+}
+
+// BlaSparseCSR.c:1357: 1.0 A + 0.0 A^T by the reference's fasp_blas_dcsr_add -- row i is A's row in its order, then the columns only A^T has
+// in the order of A^T's row, each holding 0.0 * the transposed value; a column of A^T is looked for among the row's entries of A and the one
+// slot behind them (the reference's loop bound), and a match adds 0.0 * the value to the first entry found.
+dCSRmat fasp_dcsr_sympart(dCSRmat* A)
+{
+    dCSRmat S;
+    std::memset(&S, 0, sizeof(S));
+    if (!A || A->row < 0 || A->col < 0 || A->nnz < 0) return S;
+    S.row = A->row; S.col = A->col;
+    S.IA = zalloc<int>((size_t)A->row + 1);
+    if (A->row != A->col) {   // (the reference: "Matrix sizes do not match!", the result left undefined)
+        std::printf("### ERROR: Matrix sizes do not match!\n");
+        return S;
+    }
+    if (A->nnz == 0) return S;
+    std::vector<int> tia, tja;
+    std::vector<double> tval;
+    csr_transpose(A, tia, tja, tval);
+    const double alpha = 1.0, beta = 0.0;
+    const size_t cap = (size_t)A->nnz * 2;
+    std::vector<int> cj(cap, -1);
+    std::vector<double> cv(cap, 0.0);
+    int count = 0;
+    for (int i = 0; i < A->row; ++i) {
+        const int start = count;
+        int countrow = 0;
+        for (int j = A->IA[i]; j < A->IA[i + 1]; ++j) { cv[(size_t)count] = alpha * A->val[j]; cj[(size_t)count] = A->JA[j]; ++count; ++countrow; }
+        for (int k = tia[(size_t)i]; k < tia[(size_t)i + 1]; ++k) {
+            bool added = false;
+            for (int l = start; l < start + countrow + 1; ++l)
+                if (tja[(size_t)k] == cj[(size_t)l]) { cv[(size_t)l] = cv[(size_t)l] + beta * tval[(size_t)k]; added = true; break; }
+            if (!added) { cv[(size_t)count] = beta * tval[(size_t)k]; cj[(size_t)count] = tja[(size_t)k]; ++count; }
+        }
+        S.IA[i + 1] = count;
+    }
+    S.nnz = count;
+    S.JA = zalloc<int>((size_t)count);
+    S.val = zalloc<double>((size_t)count);
+    std::memcpy(S.JA, cj.data(), sizeof(int) * (size_t)count);
+    std::memcpy(S.val, cv.data(), sizeof(double) * (size_t)count);
+    return S;
+}
+
+void fasp_dcsr_shift(dCSRmat* A, const int offset)   // BlaSparseCSR.c:1212
+{
+    if (!A || !A->IA) return;
+    for (int i = 0; i < A->row + 1; ++i) A->IA[i] += offset;
+    if (A->JA) for (int i = 0; i < A->nnz; ++i) A->JA[i] += offset;
+}
+
+// BlaSparseUtil.c:907 (A 1-based; only its pattern is read).  A node is taken when it is unflagged as the natural-order pass reaches it: a
+// row that does not name itself leaves flag[i] = 1 and is taken, one that does has set flag[i] = -1 on itself and is taken too -- the test
+// is `if (flag[i])` -- so a neighbour taken earlier never turns a node down; what keeps a node out is having been flagged by an earlier root.
+ivector fasp_sparse_mis(dCSRmat* A)
+{
+    ivector MIS{0, nullptr};
+    if (!A || A->row <= 0) return MIS;
+    const int n = A->row;
+    std::vector<int> flag((size_t)n, 0);
+    int* work = zalloc<int>((size_t)n);
+    int count = 0;
+    for (int i = 0; i < n; ++i) {
+        if (flag[(size_t)i] != 0) continue;
+        flag[(size_t)i] = 1;
+        const int rb = A->IA[i] - 1, re = A->IA[i + 1] - 1;
+        for (int j = rb; j < re; ++j)
+            if (flag[(size_t)A->JA[j] - 1] > 0) { flag[(size_t)i] = -1; break; }
+        if (flag[(size_t)i]) {
+            work[count++] = i;
+            for (int j = rb; j < re; ++j) flag[(size_t)A->JA[j] - 1] = -1;
+        }
+    }
+    MIS.row = count;
+    MIS.val = work;
+    return MIS;
+}
+
+int fasp_swz_dcsr_setup(SWZ_data* swzdata, SWZ_param* swzparam)   // BlaSchwarzSetup.c:46
+{
+    if (!swzdata || !swzparam) return ERROR_INPUT_PAR;
+    const dCSRmat A = swzdata->A;
+    const int n = A.row, maxlev = swzparam->SWZ_maxlvl;
+    // nothing of the caller's struct but A is read; everything else is (re)initialised
+    swzdata->nblk = 0; swzdata->iblock = swzdata->jblock = nullptr; swzdata->rhsloc = nullptr;
+    swzdata->rhsloc1 = dvector{0, nullptr}; swzdata->xloc1 = dvector{0, nullptr};
+    swzdata->au = swzdata->al = nullptr; swzdata->SWZ_type = 0; swzdata->blk_solver = 0; swzdata->memt = 0;
+    swzdata->mask = nullptr; swzdata->maxbs = 0; swzdata->maxa = nullptr; swzdata->blk_data = nullptr; swzdata->mumps = nullptr;
+    swzdata->swzparam = swzparam;
+    if (A.row != A.col) { say("### ERROR: fasp_swz_dcsr_setup: the matrix is %d x %d, not square\n", A.row, A.col); return ERROR_INPUT_PAR; }
+    if (maxlev < 0) { say("### ERROR: fasp_swz_dcsr_setup: SWZ_maxlvl = %d is negative\n", maxlev); return ERROR_INPUT_PAR; }
+    if (n <= 0 || !A.IA || (A.nnz > 0 && (!A.JA || !A.val))) { say("### ERROR: fasp_swz_dcsr_setup: empty matrix\n"); return ERROR_INPUT_PAR; }
+    if (A.IA[0] != 1 || A.IA[n] != A.nnz + 1) { say("### ERROR: fasp_swz_dcsr_setup: the matrix is not 1-based (fasp_dcsr_shift(A, 1) first)\n"); return ERROR_INPUT_PAR; }
+    for (int k = 0; k < A.nnz; ++k)
+        if (A.JA[k] < 1 || A.JA[k] > n) { say("### ERROR: fasp_swz_dcsr_setup: column %d of entry %d is outside 1 .. %d\n", A.JA[k], k, n); return ERROR_INPUT_PAR; }
+
+    int* maxa   = zalloc<int>((size_t)n + 1);
+    int* mask   = zalloc<int>((size_t)n);
+    int* iblock = zalloc<int>((size_t)n + 1);
+    std::vector<int> scratch((size_t)n);
+    dCSRmat A1 = A;
+    ivector MIS = fasp_sparse_mis(&A1);
+    int nlvl = 0;
+    long long nsizeall = 0;
+    int maxbs = 0;
+    for (int i = 0; i < MIS.row; ++i) {   // first pass: the sizes
+        swz_level(MIS.val[i], &A, mask, &nlvl, maxa, scratch.data(), maxlev);
+        nsizeall += maxa[nlvl];
+        maxbs = std::max(maxbs, maxa[nlvl]);
+    }
+    const int nblk = MIS.row;
+    auto give_up = [&](int code) { std::free(maxa); std::free(mask); std::free(iblock); std::free(MIS.val); return code; };
+    if (maxbs > CSR_SWZ_MAX_BS) {
+        say("### ERROR: fasp_swz_dcsr_setup: the largest block has %d rows, more than the %d this library serves\n", maxbs, CSR_SWZ_MAX_BS);
+        return give_up(ERROR_INPUT_PAR);
+    }
+    if (nsizeall + n > 0x7fffffffLL) { say("### ERROR: fasp_swz_dcsr_setup: the blocks have more than 2^31 - 1 members\n"); return give_up(ERROR_INPUT_PAR); }
+    int* jblock = zalloc<int>((size_t)(nsizeall + n));
+    maxa[0] = 0; iblock[0] = 0;
+    int* jb = jblock;
+    for (int i = 0; i < nblk; ++i) {      // second pass: the members
+        swz_level(MIS.val[i], &A, mask, &nlvl, maxa, jb, maxlev);
+        iblock[i + 1] = iblock[i] + maxa[nlvl];
+        jb += maxa[nlvl];
+    }
+    std::free(MIS.val);
+
+    // SWZ_block (BlaSchwarzSetup.c:521): one matrix per block, rows and columns in jblock order, entries in A's entry order
+    dCSRmat* blk = zalloc<dCSRmat>((size_t)nblk);
+    const int *ia = A.IA, *ja = A.JA;
+    for (int is = 0; is < nblk; ++is) {
+        const int ibl0 = iblock[is], nloc = iblock[is + 1] - ibl0;
+        int count = 0;
+        for (int i = 0; i < nloc; ++i) { const int ki = jblock[ibl0 + i]; count += ia[ki + 1] - ia[ki]; mask[ki] = i + 1; }
+        dCSRmat B;
+        B.row = nloc; B.col = nloc;
+        B.IA = zalloc<int>((size_t)nloc + 1);
+        B.JA = zalloc<int>((size_t)count);
+        B.val = zalloc<double>((size_t)count);
+        int nnz = 0;
+        for (int i = 0; i < nloc; ++i) {
+            const int ki = jblock[ibl0 + i];
+            for (int kij = ia[ki] - 1; kij < ia[ki + 1] - 1; ++kij) {
+                const int j = mask[ja[kij] - 1];
+                if (j != 0) { B.JA[nnz] = j - 1; B.val[nnz] = A.val[kij]; ++nnz; }
+            }
+            B.IA[i + 1] = nnz;
+        }
+        B.nnz = nnz;
+        blk[is] = B;
+        for (int i = 0; i < nloc; ++i) mask[jblock[ibl0 + i]] = 0;
+    }
+
+    swzdata->maxbs   = maxbs;
+    swzdata->xloc1   = dvector{maxbs, zalloc<double>((size_t)maxbs)};
+    swzdata->rhsloc1 = dvector{maxbs, zalloc<double>((size_t)maxbs)};
+    swzdata->blk_data = blk;
+    swzdata->nblk     = nblk;
+    swzdata->iblock   = iblock;
+    swzdata->jblock   = jblock;
+    swzdata->mask     = mask;
+    swzdata->maxa     = maxa;
+    swzdata->SWZ_type = swzparam->SWZ_type;
+    return FASP_SUCCESS;
+}
+
+}  // extern "C"

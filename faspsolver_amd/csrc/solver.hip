@@ -167,6 +167,7 @@ static inline int vec_grid(int n)
 
 #include "bsr.hip.h"
 #include "str_common.hip.h"
+#include "csr_swz.hip.h"
 #include "str.hip.h"
 #include "str_ilu.hip.h"
 #include "str_sweep.hip.h"
@@ -1278,6 +1279,26 @@ bool bind_diag_csr(precond* pc, int n, int, PcState& S, KOps& K, int* st)
     };
     return true;
 }
+// the reference's Schwarz preconditioner (PreCSR.c:371): recognised by its address.  The blocks of its SWZ_data are made resident at the
+// first use (uploaded and factored on the device) and stay so until fasp_swz_data_free; per application z = 0 and the sweeps of SWZ_type,
+// no host traffic.  Data the sweeps refuse ends the solve (ERROR_INPUT_PAR); data for another matrix size leaves it a foreign host function.
+bool bind_swz_csr(precond* pc, int n, int, PcState&, KOps& K, int* st)
+{
+    if (!(pc && pc->data && pc->fct == fasp_precond_swz)) return false;
+    const SWZ_data* d = static_cast<const SWZ_data*>(pc->data);
+    if (d->A.row != n) return false;
+    CsrSwzDev* M = csr_swz_device_of("fasp_precond_swz", d, st);
+    if (!M) return true;
+    if (csr_swz_refuse_stopped("fasp_precond_swz", *M) < 0) { *st = ERROR_INPUT_PAR; return true; }
+    const int type = d->SWZ_type;
+    K.pc = [M, type](double* in, double** out) { *out = M->x; return M->precond(type, in, M->x); };
+    return true;
+}
+// the CSR family's device preconditioners besides its ILU and AMG: Schwarz and the diagonal
+bool bind_pc_csr(precond* pc, int n, int nb, PcState& S, KOps& K, int* st)
+{
+    return bind_swz_csr(pc, n, nb, S, K, st) || bind_diag_csr(pc, n, nb, S, K, st);
+}
 // block-diagonal preconditioner of the reference (PreBSR.c:49): z_i = Dinv_i r_i on the device
 bool bind_diag_bsr(precond* pc, int n, int nb, PcState& S, KOps& K, int* st)
 {
@@ -1358,7 +1379,7 @@ IluDev* ilu_lookup_none(precond*, int, std::unique_ptr<IluDev, void (*)(IluDev*)
 constexpr unsigned K_OFFER_STR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_MinRes);
 
 //                              fmt        ctx_first bad_bsr_dies refuse_multi_rank refuse_empty find_amg          borrow_resident fused_mxv_dot bind_diag      ilu_lookup          handle_ilu_checked mf_texts offered
-const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_diag_csr, ilu_of_precond,     false,             false,   K_OFFER_ALL};
+const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_pc_csr,   ilu_of_precond,     false,             false,   K_OFFER_ALL};
 const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR};
 const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_pc_str,   ilu_lookup_none,    false,             false,   K_OFFER_STR};
 const KFamily FAMILY_MATFREE = {"MatFree", true,     false,       true,             true,        find_amg_matfree, false,          false,        nullptr,       ilu_of_precond,     false,             true,    K_OFFER_MATFREE};
@@ -1766,6 +1787,7 @@ int fasp_solver_dbsr_krylov_diag(dBSRmat* A, dvector* b, dvector* x, ITS_param* 
 }
 
 #include "str_api.hip.h"
+#include "csr_swz_api.hip.h"
 
 // ---------------------------------------------------------------------------
 // Matrix-free interface of the reference (fasp.h:1109 mxv_matfree, SolMatFree.c): Krylov methods

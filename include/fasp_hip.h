@@ -279,7 +279,13 @@ typedef struct {            /* fasp.h:404  ILU_param */
     double ILU_relax;
     double ILU_permtol;
 } ILU_param;
-struct SWZ_param_;          /* fasp.h:430: only ever a pointer here */
+typedef struct SWZ_param_ { /* fasp.h:430  SWZ_param */
+    short print_level;
+    short SWZ_type;
+    int   SWZ_maxlvl;
+    int   SWZ_mmsize;
+    int   SWZ_blksolver;
+} SWZ_param;
 typedef struct { int job; } Mumps_data;            /* fasp.h:596 */
 typedef struct { void* pt[64]; } Pardiso_data;     /* fasp.h:623 */
 typedef struct {            /* fasp.h:651  ILU_data */
@@ -631,7 +637,7 @@ int fasp_hip_amg_solve(fasp_hip_amg* h, const dvector* b, dvector* x, const AMG_
  * safeguards; SpMV, BLAS-1 and orthogonalisation run on the device.  pc == NULL: no
  * preconditioner.  pc->fct == fasp_hip_precond_fct: the whole iteration stays in HBM.
  * Any other pc->fct is called as a host function on host copies of r and z (one PCIe round
- * trip per application) -- e.g. a reference preconditioner (Schwarz) kept on the CPU.  fasp_precond_ilu / _forward /
+ * trip per application) -- e.g. a reference preconditioner kept on the CPU.  fasp_precond_swz, fasp_precond_ilu / _forward /
  * _backward are recognised by their address and applied on the device (triangular solves in HBM). */
 int fasp_solver_dcsr_pcg(dCSRmat* A, dvector* b, dvector* u, precond* pc, const double tol,
                          const double abstol, const int MaxIt, const short StopType, const short PrtLvl);
@@ -840,7 +846,7 @@ void fasp_smoother_dcsr_L1diag(dvector* u, const int i_1, const int i_n, const i
  * ILU as a smoother of the block AMG cycle: AMG_param.ILU_levels > 0 with fasp_solver_dbsr_krylov_amg, the fasp_hip_bsr_*
  * handles and fasp_hip_bsr_precond_setup factors the levels below ILU_levels on the host (PreAMGSetupUABSR.c:149-179) and
  * smooths them on the device with one ILU step + block Gauss-Seidel sweeps (PreMGCycle.c:321-326); one GPU only.  The
- * scalar AMG cycle (fasp_solver_dcsr_krylov_amg with ILU_levels > 0) and Schwarz stay out of scope; structured ILU: fasp_ilu_dstr_setup0 / _setup1 above. */
+ * scalar AMG cycle (fasp_solver_dcsr_krylov_amg with ILU_levels > 0) and Schwarz smoothing inside the cycles (SWZ_levels > 0) stay out of scope; structured ILU: fasp_ilu_dstr_setup0 / _setup1 above. */
 void  fasp_param_ilu_init(ILU_param* iluparam);                                     /* AuxParam.c:595 */
 void  fasp_ilu_data_create(const int iwk, const int nwork, ILU_data* iludata);      /* PreDataInit.c:411 */
 void  fasp_ilu_data_free(ILU_data* iludata);                                        /* PreDataInit.c:445 */
@@ -863,6 +869,34 @@ void  fasp_smoother_dbsr_ilu(dBSRmat* A, dvector* b, dvector* x, void* data);   
 /* SolWrapper.c:326: ILUk(0)-preconditioned VFGMRES on a caller's BSR arrays (Fortran calling convention) */
 void  fasp_fwrapper_dbsr_krylov_ilu_(int* n, int* nnz, int* nb, int* ia, int* ja, double* a, double* b, double* u,
                                      double* tol, int* maxit, int* ptrlvl);
+
+/* The overlapping (multiplicative) Schwarz method of a CSR matrix.  The host side needs no GPU and leaves the
+ * reference's arrays, entry order included: fasp_dcsr_sympart (1.0 A + 0.0 A^T: the symmetrised pattern with A's values), fasp_dcsr_shift,
+ * fasp_sparse_mis (A 1-based; the greedy pass in natural order) and fasp_swz_dcsr_setup, which reads swzdata->A (1-BASED, square) and fills
+ * nblk, iblock, jblock, maxbs, mask, maxa, blk_data, rhsloc1, xloc1, SWZ_type and swzparam; the members the reference leaves uninitialised
+ * (mumps, au, al, rhsloc, memt, blk_solver) are zeroed.  Refused with a message and ERROR_INPUT_PAR before any device work: a block of more
+ * than 256 rows, SWZ_maxlvl < 0, A.row != A.col.  SWZ_blksolver is accepted with any value and ignored: the device always solves a block
+ * directly, by a dense LU with row interchanges (the reference build without UMFPACK / MUMPS solves it with GMRES to 1e-8; with a direct
+ * solver compiled in it is exact as here).  SWZ_mmsize is never read, as in the reference.
+ * fasp_dcsr_swz_forward / _backward: one sweep over the blocks 0 .. nblk-1 / in reverse on host vectors; for each block
+ * rhs_i = b[k_i] - sum val x[k_j] over the entries of row k_i outside the block, the block solve, x[k_i] = u_i.  The first sweep of an
+ * SWZ_data uploads it and factors every block on the device; the copy stays resident, found by the struct's address, until
+ * fasp_swz_data_free.  A block whose factorisation meets a pivot below 1e-20 is refused (exit with ERROR_INPUT_PAR from the void entries,
+ * that code from the solver), its index printed; a factor store that does not fit the device: ERROR_ALLOC_MEM.
+ * fasp_precond_swz (data: SWZ_data*): z = 0, b = r, then backward (SWZ_type 2), forward and backward (3) or forward (anything else).
+ * Handed to one of this library's CSR Krylov methods it is recognised by its address and the whole iteration stays in HBM; called
+ * directly (a foreign Krylov method) it stages r and z per application.  fasp_solver_dcsr_krylov_swz: sympart, shift, setup, solve, free.
+ * Without a device the computing entries refuse to run (ERROR_MISC).  Schwarz smoothing inside the AMG cycles (SWZ_levels > 0) stays refused. */
+void    fasp_param_swz_init(SWZ_param* swzparam);                                           /* AuxParam.c:617 */
+dCSRmat fasp_dcsr_sympart(dCSRmat* A);                                                      /* BlaSparseCSR.c:1357 */
+void    fasp_dcsr_shift(dCSRmat* A, const int offset);                                      /* BlaSparseCSR.c:1212 */
+ivector fasp_sparse_mis(dCSRmat* A);                                                        /* BlaSparseUtil.c:907 */
+int     fasp_swz_dcsr_setup(SWZ_data* swzdata, SWZ_param* swzparam);                        /* BlaSchwarzSetup.c:46 */
+void    fasp_dcsr_swz_forward(SWZ_data* swzdata, SWZ_param* swzparam, dvector* x, dvector* b);   /* BlaSchwarzSetup.c:218 */
+void    fasp_dcsr_swz_backward(SWZ_data* swzdata, SWZ_param* swzparam, dvector* x, dvector* b);  /* BlaSchwarzSetup.c:328 */
+void    fasp_precond_swz(double* r, double* z, void* data);                                 /* PreCSR.c:371 */
+void    fasp_swz_data_free(SWZ_data* swzdata);                                              /* PreDataInit.c:494 */
+int     fasp_solver_dcsr_krylov_swz(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam, SWZ_param* schparam);   /* SolCSR.c:401 */
 
 /* The AMG preconditioner as a `precond` -- the role of fasp_precond_setup(PREC_AMG, ..)
  * (PreCSR.c:46) + fasp_precond_amg (PreCSR.c:416).  The returned object can be handed to the

@@ -263,6 +263,23 @@ double fasp_hip_time_str_sweep(const dSTRmat* A, int kind, int order, const int*
 int  fasp_hip_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, const double* b, double* u, int nsweeps, int* info);
 int  fasp_hip_str_swz_levels(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int* visit, int* level, int cap);
 int  fasp_hip_time_str_swz(const dSTRmat* A, const int* neigh, int nneigh, const int* order, int reps, double* ms_factor, double* ms_sweep, int* info);
+/* The CSR overlapping Schwarz sweeps on a resident copy (csrc/csr_swz.hip.h).  swz: an SWZ_data that
+ * fasp_swz_dcsr_setup has filled.
+ * fasp_hip_csr_swz_levels (pure host code): level[v] (`cap` ints) = the dependency level of block v in the forward (backward 0) or the
+ * reversed (backward != 0) sequence; returns the number of levels, ERROR_INPUT_PAR for data the sweeps refuse.
+ * fasp_hip_csr_swz: the copy of swz is made resident (uploaded and factored at its first use), then nsweeps times dir (1 forward, 2 backward,
+ * 3 forward then backward) from the caller's x with right-hand side b; x back.  info (8 ints, may be NULL): {levels forward, levels backward,
+ * launches of this call, nblk, maxbs, blocks with a row interchange, blocks whose factorisation stopped, factorisations this resident copy has
+ * run (1 however often it is used)}.  fac / piv (may be NULL): the factors as stored, block v column by column (entry (r, c) at c m + r) at
+ * the sum of m^2 over the blocks before it, and the pivots at iblock[v].  ERROR_INPUT_PAR, x untouched: refused data, a stopped block
+ * included (info, fac and piv are filled all the same); ERROR_ALLOC_MEM: the store does not fit; ERROR_MISC: no device.
+ * fasp_hip_csr_swz_resident_count: SWZ_data with a device copy now.
+ * fasp_hip_time_csr_swz: HIP-event milliseconds, mean over `reps` after one warm-up, ms[0] of the factorisation, ms[1] of a forward and ms[2]
+ * of a backward sweep; bytes[0] = the bytes of the factor store, bytes[1] = what a forward sweep moves at least; info as above. */
+int  fasp_hip_csr_swz_levels(const SWZ_data* swz, int backward, int* level, int cap);
+int  fasp_hip_csr_swz(SWZ_data* swz, int dir, const double* b, double* x, int nsweeps, int* info, double* fac, int* piv);
+int  fasp_hip_csr_swz_resident_count(void);
+int  fasp_hip_time_csr_swz(SWZ_data* swz, int reps, double* ms, double* bytes, int* info);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
