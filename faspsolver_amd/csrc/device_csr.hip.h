@@ -59,8 +59,18 @@ struct DevCSR {
     double*        sell_tab = nullptr;
     int            sell_nv = 0, sell_obits = 0, sell_nslice = 0;
     long long      sell_slots = 0;
+    // k_csr_rgroup (kernels5.hip.h): groups of rg_R consecutive rows over the union of their columns (build_rgroup); beside the plain copy
+    unsigned*      rg_code = nullptr;   // per group: chunk value offsets, then one word per union column
+    double*        rg_val = nullptr;    // the values in the walk's order
+    int*           rg_meta = nullptr;   // per group {word offset, value offset, smallest column, chunks} + a closing entry
+    int            rg_R = 0, rg_ng = 0;
+    long long      rg_words = 0;
     void    release()
     {
+        if (rg_code) (void)hipFree(rg_code);
+        if (rg_val) (void)hipFree(rg_val);
+        if (rg_meta) (void)hipFree(rg_meta);
+        rg_code = nullptr; rg_val = nullptr; rg_meta = nullptr; rg_R = rg_ng = 0; rg_words = 0;
         if (sell_code) (void)hipFree(sell_code);
         if (sell_meta) (void)hipFree(sell_meta);
         if (sell_rlen) (void)hipFree(sell_rlen);
@@ -926,6 +936,189 @@ static void sell_decode_host(const SellHost& S, int nrow, int* ia, int* ja, doub
     }
 }
 
+// Row-group coding (kernels5.hip.h, k_csr_rgroup) of a long-row square operator in the numbering its device copy uses: groups of R
+// consecutive rows walked over the sorted union of their columns.  code = per group {nch + 1 value offsets of its chunks of 64 union
+// columns, relative to the group's first value; one word per union column: column - the group's smallest column | row mask << (32 - R)},
+// padded at the very end to a multiple of four words with the word 0; val = the values without fill, chunk by chunk, inside a chunk row
+// by row in union order (+ two zeros at the end: the last 16-byte piece); meta = per group {word offset, value offset, smallest column,
+// chunks} + one closing {words, values, 0, 0}.  A row's entries come back sorted by column (the order of the sorted device copy).  Lossless.
+// Refused (why_not): 1 the operator is not square; 2 mean row shorter than RG_MIN_ROW entries; 3 a group's columns span more than 65 535;
+// 4 a row holds the same column twice; 5 entries / union columns (the mean reuse of a gather) below min_reuse.
+constexpr int    RG_MIN_ROW   = 128;
+constexpr int    RG_ROWS      = 8;     // rows per group unless fasp_hip_tune("rgroup_rows", 16) asks for 16 (measured: profiles/rgroup.txt)
+constexpr double RG_W4_MIN_ROW = 256.0, RG_W8_MIN_ROW = 1000.0;   // waves per group: 2 below a mean row of 256 entries, 4 below 1 000, else 8, unless fasp_hip_tune("rgroup_waves", 2 | 4 | 8)
+constexpr double RG_MIN_REUSE = 3.0;   // below it the form would also read more bytes than the 10 per entry of the 16-bit-column copy
+struct RGroupHost {
+    int R = 0, ng = 0;
+    long long words = 0, chunks = 0, ucols = 0;   // 32-bit words of code (without the end padding), chunks, union columns
+    std::vector<int> meta;
+    Buf<unsigned>    code;
+    Buf<double>      val;
+};
+static double rgroup_bytes(long long nnz, long long words, int ng) { return 8.0 * (double)nnz + 4.0 * (double)words + 16.0 * (ng + 1.0); }
+static bool build_rgroup(const HostCSR& M, int R, double min_reuse, RGroupHost& G, int* why_not)
+{
+    int dummy = 0;
+    int& why = why_not ? *why_not : dummy;
+    G = RGroupHost();
+    G.R = R;
+    if (M.row != M.col) { why = 1; return false; }
+    if (M.row <= 0 || M.nnz <= 0 || (double)M.nnz < (double)RG_MIN_ROW * M.row) { why = 2; return false; }
+    const int n = M.row, ng = (n + R - 1) / R, sh = 32 - R;
+    std::vector<std::vector<unsigned>> gcode((size_t)ng);   // per group: chunk offsets + words
+    std::vector<int> gbase((size_t)ng, 0), gnch((size_t)ng, 0);
+    G.val.alloc((size_t)M.nnz + 2);
+    G.val[(size_t)M.nnz] = 0.0; G.val[(size_t)M.nnz + 1] = 0.0;
+    int bad = 0;   // the smallest refusal code met (0: none)
+#pragma omp parallel
+    {
+        std::vector<unsigned> mask((size_t)65536, 0u);   // per column offset: rows of the group that hold it
+        std::vector<int>      pos((size_t)65536, 0);     // ... its place in the union
+        std::vector<unsigned short> touched;
+        std::vector<int> slot;                           // per (union column, row): the value's place in the group
+        int mybad = 0;
+#pragma omp for schedule(dynamic, 16)
+        for (int g = 0; g < ng; ++g) {
+            const int r0 = g * R, r1 = std::min(n, r0 + R), k0 = M.ia[r0], k1 = M.ia[r1];
+            std::vector<unsigned>& out = gcode[(size_t)g];
+            if (k1 <= k0) { out.assign(1, 0u); continue; }
+            int lo = M.ja[k0], hi = lo;
+            for (int k = k0 + 1; k < k1; ++k) { lo = std::min(lo, M.ja[k]); hi = std::max(hi, M.ja[k]); }
+            if (hi - lo > 65535) { mybad = mybad ? std::min(mybad, 3) : 3; continue; }
+            gbase[(size_t)g] = lo;
+            touched.clear();
+            bool dup = false;
+            for (int r = r0; r < r1; ++r)
+                for (int k = M.ia[r]; k < M.ia[r + 1]; ++k) {
+                    const int off = M.ja[k] - lo;
+                    const unsigned bit = 1u << (r - r0);
+                    if (!mask[(size_t)off]) touched.push_back((unsigned short)off);
+                    if (mask[(size_t)off] & bit) dup = true;
+                    mask[(size_t)off] |= bit;
+                }
+            if (dup) {
+                mybad = mybad ? std::min(mybad, 4) : 4;
+                for (unsigned short t : touched) mask[t] = 0u;
+                continue;
+            }
+            std::sort(touched.begin(), touched.end());
+            const int nu = (int)touched.size(), nch = (nu + 63) / 64;
+            out.resize((size_t)nch + 1 + nu);
+            gnch[(size_t)g] = nch;
+            slot.assign((size_t)nu * R, -1);
+            int next = 0;
+            for (int c = 0; c < nch; ++c) {
+                out[(size_t)c] = (unsigned)next;
+                const int u1 = std::min(nu, 64 * c + 64);
+                for (int r = 0; r < R; ++r)
+                    for (int u = 64 * c; u < u1; ++u)
+                        if (mask[touched[(size_t)u]] >> r & 1u) slot[(size_t)u * R + r] = next++;
+            }
+            out[(size_t)nch] = (unsigned)next;   // == k1 - k0
+            for (int u = 0; u < nu; ++u) {
+                pos[touched[(size_t)u]] = u;
+                out[(size_t)nch + 1 + u] = (unsigned)touched[(size_t)u] | (mask[touched[(size_t)u]] << sh);
+            }
+            for (int r = r0; r < r1; ++r)
+                for (int k = M.ia[r]; k < M.ia[r + 1]; ++k)
+                    G.val[(size_t)k0 + (size_t)slot[(size_t)pos[(size_t)(M.ja[k] - lo)] * R + (r - r0)]] = M.val[k];
+            for (unsigned short t : touched) mask[t] = 0u;
+        }
+#pragma omp critical
+        if (mybad) bad = bad ? std::min(bad, mybad) : mybad;
+    }
+    if (bad) { why = bad; return false; }
+    G.ng = ng;
+    G.meta.assign(4 * ((size_t)ng + 1), 0);
+    long long w = 0;
+    for (int g = 0; g < ng; ++g) {
+        const std::vector<unsigned>& c = gcode[(size_t)g];
+        const int r0 = g * R;
+        const int nch = gnch[(size_t)g];
+        G.meta[4 * (size_t)g] = (int)w; G.meta[4 * (size_t)g + 1] = M.ia[r0]; G.meta[4 * (size_t)g + 2] = gbase[(size_t)g]; G.meta[4 * (size_t)g + 3] = nch;
+        w += (long long)c.size();
+        G.chunks += nch;
+        G.ucols += (long long)c.size() - (nch + 1);
+    }
+    if (w >= (1ll << 31) - 8) { why = 2; return false; }
+    G.meta[4 * (size_t)ng] = (int)w; G.meta[4 * (size_t)ng + 1] = M.nnz;
+    G.words = w;
+    if ((double)M.nnz < min_reuse * (double)G.ucols) { why = 5; return false; }
+    G.code.alloc((size_t)((w + 3) & ~3ll) + 4);
+    for (long long i = w; i < ((w + 3) & ~3ll) + 4; ++i) G.code[(size_t)i] = 0u;
+#pragma omp parallel for schedule(static)
+    for (int g = 0; g < ng; ++g) std::copy(gcode[(size_t)g].begin(), gcode[(size_t)g].end(), G.code.data() + G.meta[4 * (size_t)g]);
+    why = 0;
+    return true;
+}
+// y = A x over the coded form in k_csr_rgroup's order with NW waves per group: per wave its share of the chunks, per lane (union column) and
+// row a sum in chunk order; per lane the waves' parts in wave order; the 64 lanes by es_group_sum's tree (row_shr 1, 2, 4, 8 inside rows
+// of 16 lanes, then lane 15 of row 0 / 2 into rows 1 / 3, then lane 31 into rows 2 and 3: the total ends in lane 63)
+static void rgroup_mxv_host(const RGroupHost& G, int nrow, int NW, const double* x, double* y)
+{
+    const int R = G.R, sh = 32 - R;
+    for (int g = 0; g < G.ng; ++g) {
+        const int woff = G.meta[4 * (size_t)g], voff = G.meta[4 * (size_t)g + 1], cbase = G.meta[4 * (size_t)g + 2], nch = G.meta[4 * (size_t)g + 3];
+        const int len = G.meta[4 * (size_t)g + 4] - woff - (nch + 1);
+        const unsigned* coff = G.code.data() + woff;
+        const unsigned* wd = coff + nch + 1;
+        double sum[16][64];
+        for (int w = 0; w < NW; ++w) {
+            double acc[16][64];
+            for (int r = 0; r < R; ++r)
+                for (int l = 0; l < 64; ++l) acc[r][l] = 0.0;
+            for (int c = nch * w / NW; c < nch * (w + 1) / NW; ++c) {
+                int at = voff + (int)coff[c];
+                for (int r = 0; r < R; ++r)
+                    for (int l = 0; l < 64 && 64 * c + l < len; ++l) {
+                        const unsigned word = wd[64 * c + l];
+                        if (!((word >> (sh + r)) & 1u)) continue;
+                        const double p = G.val[(size_t)at++] * x[cbase + (int)(word & 0xffffu)];
+                        acc[r][l] = acc[r][l] + p;
+                    }
+            }
+            for (int r = 0; r < R; ++r)
+                for (int l = 0; l < 64; ++l) sum[r][l] = w == 0 ? acc[r][l] : sum[r][l] + acc[r][l];
+        }
+        for (int r = 0; r < R && g * R + r < nrow; ++r) {
+            double* v = sum[r];
+            double t[64];
+            for (int s = 1; s <= 8; s <<= 1) {
+                for (int l = 0; l < 64; ++l) t[l] = v[l] + ((l & 15) >= s ? v[l - s] : 0.0);
+                for (int l = 0; l < 64; ++l) v[l] = t[l];
+            }
+            for (int l = 0; l < 64; ++l) t[l] = v[l] + (((l >> 4) & 1) ? v[(l & ~15) - 1] : 0.0);
+            for (int l = 0; l < 64; ++l) v[l] = t[l];
+            for (int l = 0; l < 64; ++l) t[l] = v[l] + (l >= 32 ? v[31] : 0.0);
+            y[g * R + r] = t[63];
+        }
+    }
+}
+// the coded form back to CSR, every row sorted by column (ia: nrow + 1; ja, val: nnz)
+static void rgroup_decode_host(const RGroupHost& G, int nrow, int* ia, int* ja, double* val)
+{
+    const int R = G.R, sh = 32 - R;
+    int k = 0;
+    ia[0] = 0;
+    for (int g = 0; g < G.ng; ++g) {
+        const int woff = G.meta[4 * (size_t)g], voff = G.meta[4 * (size_t)g + 1], cbase = G.meta[4 * (size_t)g + 2], nch = G.meta[4 * (size_t)g + 3];
+        const int len = G.meta[4 * (size_t)g + 4] - woff - (nch + 1);
+        const unsigned* coff = G.code.data() + woff;
+        const unsigned* wd = coff + nch + 1;
+        for (int r = 0; r < R && g * R + r < nrow; ++r) {
+            for (int c = 0; c < nch; ++c) {
+                int at = voff + (int)coff[c];   // row r's values of the chunk lie behind those of the rows 0 .. r - 1
+                const int u1 = std::min(len, 64 * c + 64);
+                for (int q = 0; q < r; ++q)
+                    for (int u = 64 * c; u < u1; ++u) at += (int)((wd[u] >> (sh + q)) & 1u);
+                for (int u = 64 * c; u < u1; ++u)
+                    if ((wd[u] >> (sh + r)) & 1u) { ja[k] = cbase + (int)(wd[u] & 0xffffu); val[k] = G.val[(size_t)at++]; ++k; }
+            }
+            ia[g * R + r + 1] = k;
+        }
+    }
+}
+
 static int upload_sell(const HostCSR& H, DevCSR& D)
 {
     static const bool on = !(std::getenv("FASP_HIP_SELL") && std::atoi(std::getenv("FASP_HIP_SELL")) == 0);
@@ -1110,8 +1303,34 @@ static int upload_csr(const HostCSR& H, DevCSR& D)
 }
 
 // development knobs (fasp_hip_tune): -1 = automatic
-struct Tuning { int swz_run = -1, swz_run_width = 16, ilu_smooth_fused = 1, gen2 = 2, ws2_bpc = 3, maxgrid = -1, xcd = 16, nt = 1, kind = -1, lanes = -1, wrows = -1, wcap = -1, compress = 1, rpl = -1, lds_tab = 1, xcd_pat = 64, spcg_batch = 16, small_lds = 1, ja16 = 1, spcg_fused = 1, spcg_grid = 0, spcg_persist = 1, split_rows = 0, gs_multicolor = 0, seq_flow = 1, seq_strip_kb = 0, seq_jobs = 1, seq_spine = 1, seq_grid = 0, seq_chain = 1, seq_chain_n1 = 0, seq_chain_grid = 0, seq_chain_ref = 0, seq_test_hang = 0, seq_rest_lanes = 0, local_square = 1, fuse_zr = 1, fuse_presmooth = 1, seq_lanes = 0, xtile = 1, rp5_max = 45, rp_bpc = 5, rp_xcd = -1, rp_strip = 2, spcg_test_hang = 0, small_onewave = 4, lazy_coarse = 1, rp_stream = -1, renumber = 1, renumber_chunk = 262144, pcg_dev_beta = 1, spcg_spec = 1, ev_every = 4, pcg_fold = 1, seq_chain_touch = 8, seq_chain_touch_t1 = 1, seq_zero_skip = 1, estream = 1, es_dbg = 0, ilu_form = -1, str_ilu_form = -1, str_ilu_wgs = 0, str_sweep_form = -1, str_sweep_wgs = 0, sell = 1; };
+struct Tuning { int swz_run = -1, swz_run_width = 16, ilu_smooth_fused = 1, gen2 = 2, ws2_bpc = 3, maxgrid = -1, xcd = 16, nt = 1, kind = -1, lanes = -1, wrows = -1, wcap = -1, compress = 1, rpl = -1, lds_tab = 1, xcd_pat = 64, spcg_batch = 16, small_lds = 1, ja16 = 1, spcg_fused = 1, spcg_grid = 0, spcg_persist = 1, split_rows = 0, gs_multicolor = 0, seq_flow = 1, seq_strip_kb = 0, seq_jobs = 1, seq_spine = 1, seq_grid = 0, seq_chain = 1, seq_chain_n1 = 0, seq_chain_grid = 0, seq_chain_ref = 0, seq_test_hang = 0, seq_rest_lanes = 0, local_square = 1, fuse_zr = 1, fuse_presmooth = 1, seq_lanes = 0, xtile = 1, rp5_max = 45, rp_bpc = 5, rp_xcd = -1, rp_strip = 2, spcg_test_hang = 0, small_onewave = 4, lazy_coarse = 1, rp_stream = -1, renumber = 1, renumber_chunk = 262144, pcg_dev_beta = 1, spcg_spec = 1, ev_every = 4, pcg_fold = 1, seq_chain_touch = 8, seq_chain_touch_t1 = 1, seq_zero_skip = 1, estream = 1, es_dbg = 0, ilu_form = -1, str_ilu_form = -1, str_ilu_wgs = 0, str_sweep_form = -1, str_sweep_wgs = 0, sell = 1, rgroup = 1, rgroup_rows = 0, rgroup_waves = 0; };
 static Tuning g_tune;
+
+// The row-group form (build_rgroup) of a square long-row operator beside its plain device copy, which stays: row windows, OP_MXV_DOT and
+// the distributed path use it.  Built only while fasp_hip_tune("rgroup") is not 0; an operator a rule refuses simply has none.
+static int upload_rgroup(const HostCSR& H, DevCSR& D)
+{
+    if (g_tune.rgroup == 0 || g_oneshot_upload || H.row != H.col || (double)H.nnz < (double)RG_MIN_ROW * H.row) return FASP_SUCCESS;
+    static const bool timing = std::getenv("FASP_HIP_SETUP_TIMING") != nullptr;
+    const double t0 = wall_seconds();
+    RGroupHost G;
+    int why = 0;
+    const bool ok = build_rgroup(H, g_tune.rgroup_rows == 16 ? 16 : RG_ROWS, RG_MIN_REUSE, G, &why);
+    if (timing) std::printf("        [row groups %d x %d, %d nnz] %s (%d) R %d, %d groups, %lld chunks, reuse %.2f, %.2f bytes per entry, %.3f s\n", H.row, H.col, H.nnz,
+                            ok ? "coded" : "not coded", why, G.R, G.ng, G.chunks, G.ucols ? (double)H.nnz / (double)G.ucols : 0.0,
+                            ok ? rgroup_bytes(H.nnz, G.words, G.ng) / H.nnz : 0.0, wall_seconds() - t0);
+    if (!ok) return FASP_SUCCESS;
+    const size_t nw = (size_t)((G.words + 3) & ~3ll) + 4;
+    HIPCK(hipMalloc(&D.rg_code, sizeof(unsigned) * nw));
+    HIPCK(hipMalloc(&D.rg_val, sizeof(double) * ((size_t)H.nnz + 2)));
+    HIPCK(hipMalloc(&D.rg_meta, sizeof(int) * G.meta.size()));
+    HIPCK(hipMemcpy(D.rg_code, G.code.data(), sizeof(unsigned) * nw, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(D.rg_val, G.val.data(), sizeof(double) * ((size_t)H.nnz + 2), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(D.rg_meta, G.meta.data(), sizeof(int) * G.meta.size(), hipMemcpyHostToDevice));
+    D.rg_R = G.R; D.rg_ng = G.ng; D.rg_words = G.words;
+    if (timing) std::printf("        [row groups %d x %d] with the copy to the device %.3f s\n", H.row, H.col, wall_seconds() - t0);
+    return FASP_SUCCESS;
+}
 
 // Blocks of one kernel instantiation that are co-resident on a CU (VGPR / LDS / wave
 // limits), from the occupancy API, cached per instantiation.  The persistent grids
@@ -1145,6 +1364,31 @@ static int launch_persistent(K kernel, int ntiles, CsrArgs& a, int blocks_per_cu
     return grid;
 }
 
+// Where k_csr_rgroup replaces the kernel the plan would otherwise pick under fasp_hip_tune("rgroup", 1): on a level only where it measured
+// faster by more than the spread of repeated cold timings of that kernel (at most 1.5 us over three repeats of eight launches; one
+// outlier).  P7(256), cold, us per launch, y = A x / y -= A x / Jacobi (profiles/rgroup.txt):
+//   level (entries per row)   kernel without     8 rows, 2 waves    8 rows, 4 waves    8 rows, 8 waves    16 rows, best of 2 / 4 / 8 waves
+//   4 (191)                   49 / 50 / 54       38 / 39 / 43       39 / 40 / 45       55 / 50 / 65       43 / 46 / 52 (2)
+//   5 (390)                   56 / 54 / 57       40 / 41 / 42       37 / 38 / 40       44 / 40 / 49       41 / 43 / 46 (4)
+//   6 (710)                   58 / 60 / 62       46 / 46 / 47       42 / 42 / 43       44 / 43 / 47       45 / 46 / 49 (8)
+//   7 (1 114)                 58 / 55 / 58       44 / 44 / 45       40 / 40 / 41       39 / 40 / 42       43 / 42 / 46 (8)
+//   8 (1 356)                 40 / 39 / 41       39 / 39 / 40       33 / 33 / 34       32 / 31 / 33       33 / 33 / 34 (8)
+// Groups of 8 rows win on every level that has the copy, by 7-18 us, and beat groups of 16 on every level: 8 is the default.  (The arithmetic
+// of a chunk costs the same whether the R x 64 places of its rows are taken or not, and groups of 8 fill 47 % of them where groups of 16
+// fill 39 %.)  Waves per group: 2 below a mean row of 256 entries, 4 below 1 000, 8 from there on (RG_W4_MIN_ROW, RG_W8_MIN_ROW; level 7 is a tie
+// of 4 and 8).  A copy built with 16 rows per group is used between 256 and 1 200 entries per row, where it won by 8-15 us; on levels 4 and 8
+// it wins by less and only with one of the wave counts.
+static int rgroup_waves_auto(const DevCSR& M)
+{
+    const double avg = M.row > 0 ? (double)M.nnz / M.row : 0.0;
+    return avg >= RG_W8_MIN_ROW ? 8 : avg >= RG_W4_MIN_ROW ? 4 : 2;
+}
+static bool rgroup_measured_faster(const DevCSR& M)
+{
+    const double avg = M.row > 0 ? (double)M.nnz / M.row : 0.0;
+    return M.rg_R == 8 || (avg >= 256.0 && avg < 1200.0);
+}
+
 // The kernel ONE launch of a row operation runs.  plan_csr decides it -- the only place that does: launch_csr executes the plan, and
 // fasp_hip_amg_kernel_info, fasp_hip_matrix_op, fasp_hip_time_matrix and the (z, r) fusion of the smoother read it.  A value per
 // instantiation (but OP); the order is part of fasp_hip_csr_plan's report (fasp_hip_dev.h, tests/_csr_cases.py).
@@ -1154,7 +1398,9 @@ enum CsrKernel : int {
     CK_ROWPAT_0_1, CK_ROWPAT_0_2, CK_ROWPAT_1_1, CK_ROWPAT_1_2, CK_ROWPAT_2_1, CK_ROWPAT_2_2,   // k_csr_rowpat<OP, T, RPL>
     CK_DICT8_8, CK_DICT8_16, CK_DICT8_24,                                                   // k_csr_dict8<OP, U>
     CK_ESTREAM_4, CK_ESTREAM_8, CK_ESTREAM_16, CK_ESTREAM_32,                               // k_csr_estream<L, OP>
-    CK_ROWPAT4, CK_ROWPAT5, CK_LSTREAM, CK_XTILE, CK_SELL, CK_WSTREAM2
+    CK_ROWPAT4, CK_ROWPAT5, CK_LSTREAM, CK_XTILE, CK_SELL, CK_WSTREAM2,
+    CK_RGROUP_16_4, CK_RGROUP_16_8, CK_RGROUP_8_4, CK_RGROUP_8_8,                           // k_csr_rgroup<R, NW, OP>
+    CK_RGROUP_16_2, CK_RGROUP_8_2
 };
 struct CsrPlan {
     CsrKernel kernel;
@@ -1257,7 +1503,18 @@ static CsrPlan plan_csr(const DevCSR& M, int op, bool windowed, bool want_partia
         // 51 -> 48 us per product; on the longer rows the two tie (both sit on the gather rate of the texture-address pipe) and the row
         // kernel's epilogue is lighter.  fasp_hip_tune("estream", 2): wherever the tables exist (tests, A/B runs); 0: never.
         const bool es_rule = g_tune.estream >= 2 || (g_tune.estream == 1 && (double)M.nnz < 256.0 * M.row);
-        if (M.es_tab && es_rule && p.ja16 && !windowed && op != OP_MXV_DOT && !(jac && (want_partials || M.dup_diag)))
+        // row groups (kernels5.hip.h): one gather of x per union column of R consecutive rows.  fasp_hip_tune("rgroup", 2): wherever the coded
+        // copy exists; 1 (default): by the measured rule (rgroup_measured_faster) -- and not under fasp_hip_tune("estream", 0), which asks for
+        // the row kernel on every long-row operator (row windows against whole launches, bit for bit); 0: never, and no copy is built.
+        const bool rg_rule = g_tune.rgroup >= 2 || (g_tune.rgroup == 1 && g_tune.estream != 0 && rgroup_measured_faster(M));
+        if (M.rg_code && rg_rule && !windowed && op != OP_MXV_DOT && !(jac && (want_partials || M.dup_diag))) {
+            const int tw = g_tune.rgroup_waves, nw = tw == 2 || tw == 4 || tw == 8 ? tw : rgroup_waves_auto(M);
+            p.kernel = M.rg_R == 8 ? (nw == 2 ? CK_RGROUP_8_2 : nw == 4 ? CK_RGROUP_8_4 : CK_RGROUP_8_8) : (nw == 2 ? CK_RGROUP_16_2 : nw == 4 ? CK_RGROUP_16_4 : CK_RGROUP_16_8);
+            p.tile_rows = M.rg_R;
+            p.ja16 = p.jbase = false;
+            p.bytes = rgroup_bytes(M.nnz, M.rg_words, M.rg_ng);
+        }
+        else if (M.es_tab && es_rule && p.ja16 && !windowed && op != OP_MXV_DOT && !(jac && (want_partials || M.dup_diag)))
             // lanes per row: so that the rows a 512-entry chunk touches normally fit one pass of 64 / L rows (kernels3.hip.h)
             p.kernel = avg >= 512.0 ? CK_ESTREAM_32 : avg >= 256.0 ? CK_ESTREAM_16 : avg >= 128.0 ? CK_ESTREAM_8 : CK_ESTREAM_4;
         else
@@ -1300,6 +1557,26 @@ static int launch_sell(const DevCSR& M, CsrArgs& a)
     grid = std::max(8, (grid + 7) / 8 * 8);
     hipLaunchKernelGGL(k_csr_sell<OP>, dim3(grid), dim3(SELL_BLOCK), lds, g_ctx.stream, a);
     return grid;
+}
+
+// One workgroup of NW waves per group of R rows; an XCD's workgroups (blocks b, b + 8, ...) take one contiguous eighth of the groups.
+// LDS: a slab of 64 R doubles per wave (a chunk's values: at most R per union column).  No fused dot products: OP_MXV_DOT never gets here.
+template <int R, int NW, int OP>
+static int launch_rgroup(const DevCSR& M, CsrArgs& a)
+{
+    if constexpr (OP == OP_MXV_DOT) { (void)M; (void)a; return 0; }
+    else {
+        a.rg_code = M.rg_code; a.rg_val = M.rg_val; a.rg_meta = M.rg_meta; a.rg_ng = M.rg_ng;
+        constexpr int lds = NW * 64 * R * 8;
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_csr_rgroup<R, NW, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            attr_set = true;
+        }
+        const int grid = 8 * ((M.rg_ng + 7) / 8);
+        hipLaunchKernelGGL((k_csr_rgroup<R, NW, OP>), dim3(grid), dim3(NW * 64), lds, g_ctx.stream, a);
+        return grid;
+    }
 }
 
 // (the transfer-operator kernel has no smoother instantiations)
@@ -1420,6 +1697,12 @@ static int launch_csr(const DevCSR& M0, CsrArgs a, RowWin win = RowWin())
         case CK_XTILE:    PERSIST(k_csr_xtile<OP>);
         case CK_SELL:     return launch_sell<OP>(M, a);
         case CK_WSTREAM2: PERSIST(k_csr_wstream2<OP>);
+        case CK_RGROUP_16_4: return launch_rgroup<16, 4, OP>(M, a);
+        case CK_RGROUP_16_8: return launch_rgroup<16, 8, OP>(M, a);
+        case CK_RGROUP_8_4:  return launch_rgroup<8, 4, OP>(M, a);
+        case CK_RGROUP_8_8:  return launch_rgroup<8, 8, OP>(M, a);
+        case CK_RGROUP_16_2: return launch_rgroup<16, 2, OP>(M, a);
+        case CK_RGROUP_8_2:  return launch_rgroup<8, 2, OP>(M, a);
         default: break;   // k_csr_estream<L, OP>
     }
 #undef PERSIST

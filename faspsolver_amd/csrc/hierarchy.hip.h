@@ -462,6 +462,9 @@ static int upload_level(fasp_hip_amg* h, int l, const DistLevel* DLp)
         if (!uploaded && upload_csr(*Adev, D.A) < 0) return ERROR_ALLOC_MEM;
     }
     lap("A");
+    // the row-group form of a long-row level (k_csr_rgroup), from the operator in the numbering of the device copy
+    if (rep && HL.has_coarse && upload_rgroup(*Adev, D.A) < 0) return ERROR_ALLOC_MEM;   // (the coarsest level is solved, not smoothed)
+    lap("row groups");
     if (renum) {   // the transfer operators of the level above, now that this level's numbering is known
         if (l > 0 && h->H.L[(size_t)l - 1].has_coarse && !h->L[(size_t)l - 1].P.ia) {
             const int st = upload_transfer(h, l - 1, nullptr);

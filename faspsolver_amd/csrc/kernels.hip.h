@@ -104,6 +104,11 @@ struct CsrArgs {
     const unsigned char* sell_rlen;   // per row: its length
     const double*        sell_tab;    // the distinct values
     int                  sell_nv, sell_obits;
+    // k_csr_rgroup (kernels5.hip.h): row groups over the union of their columns, built at upload (device_csr.hip.h, build_rgroup)
+    const unsigned*      rg_code;     // per group: chunk value offsets (chunks + 1), then a word per union column: column - base | row mask << (32 - R)
+    const double*        rg_val;      // values: chunk by chunk, inside a chunk row by row in union order
+    const int*           rg_meta;     // per group {word offset, value offset, smallest column, chunks}; one closing entry
+    int                  rg_ng;       // groups
 };
 
 __device__ __forceinline__ void zx_store(const CsrArgs& a, int r, double s)

@@ -45,6 +45,7 @@
 #include "kernels2.hip.h"
 #include "kernels3.hip.h"
 #include "kernels4.hip.h"
+#include "kernels5.hip.h"
 #include "small_solvers.hip.h"
 #include "seq_split.hip.h"
 #include "seq_chain.hip.h"
@@ -2278,6 +2279,9 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "renumber_chunk")) g_tune.renumber_chunk = value; // rows per chunk inside which the balls grow (reorder.cpp)
     else if (!std::strcmp(key, "time_cold")) g_time_cold = value;
     else if (!std::strcmp(key, "estream")) g_tune.estream = value;   // long-row operators: the entry-parallel stream kernel where it measured faster (1, default: mean rows below 256 entries), wherever its tables exist (2), never (0: the row kernel); read at launch
+    else if (!std::strcmp(key, "rgroup")) g_tune.rgroup = value;     // long-row square operators: the row-group form and k_csr_rgroup never (0: no copy is built), where it measured faster (1, default; not under estream 0), wherever the copy exists (2); read at upload (0 or not) and at launch
+    else if (!std::strcmp(key, "rgroup_rows")) g_tune.rgroup_rows = value;     // ... rows per group: 8 (default) or 16; read at upload
+    else if (!std::strcmp(key, "rgroup_waves")) g_tune.rgroup_waves = value;   // ... waves per group: 2, 4 or 8 (default: by the mean row length, 2 below 256 entries, 8 from 1 000 on); read at launch
     else if (!std::strcmp(key, "sell")) g_tune.sell = value;         // value-indexed sliced-ELL form where an operator has it (1, default) or its plain-CSR kernels (0), the other codings untouched; read at launch
     else if (!std::strcmp(key, "es_dbg")) g_tune.es_dbg = value;     // (FASP_LAB_DEBUG builds: parts of the stream kernel switched off -- timings only)
     else if (!std::strcmp(key, "pcg_dev_beta")) g_tune.pcg_dev_beta = value;   // top-level PCG: (z, r), beta and alpha stay on the device, one host wait per iteration (1, default) or two (0)
@@ -2338,6 +2342,50 @@ int fasp_hip_csr_plan(const int* traits, int op, int windowed, int want_partials
     const int out[11] = {(int)p.kernel, p.family, p.tile_rows, p.bpc, p.xcd_map, p.tpp, p.nt, p.ja16, p.jbase, p.fused_zr, kernel_family(M, nullptr)};
     std::copy(out, out + 11, plan);
     if (bytes) *bytes = p.bytes;
+    return FASP_SUCCESS;
+}
+
+// ... with the traits of the row-group copy behind the 28 (fasp_hip_dev.h): rg_code set, rows per group, groups, 32-bit words of code
+int fasp_hip_csr_plan2(const int* traits, int op, int windowed, int want_partials, int* plan, double* bytes)
+{
+    FASP_ENTRY();
+    if (!traits || !plan || op < OP_MXV || op > OP_MXV_DOT) return ERROR_INPUT_PAR;
+    static double dummy[1];
+    const int* t = traits;
+    auto flag = [&](int i) -> void* { return t[i] ? dummy : nullptr; };
+    DevCSR M;
+    M.row = t[0]; M.col = t[1]; M.nnz = t[2]; M.kind = t[3]; M.lanes = t[4]; M.wrows = t[5]; M.wcap = t[6]; M.nxrows = t[7]; M.plane = t[8];
+    M.npat = t[9]; M.npent = t[10]; M.sell_nv = t[11]; M.sell_nslice = t[12]; M.sell_slots = t[13]; M.ntcols = t[14]; M.es_W = t[15]; M.es_nc = t[16];
+    M.code = (unsigned char*)flag(17); M.pat = (unsigned short*)flag(18); M.rowbase = (int*)flag(19); M.dpos = (int*)flag(20); M.dup_diag = t[21] != 0;
+    M.ja16 = (unsigned short*)flag(22); M.jbase = (int*)flag(23); M.lja16 = (unsigned short*)flag(24); M.sell_code = (unsigned*)flag(25);
+    M.es_tab = (int*)flag(26); M.es_ja16 = (unsigned short*)flag(27);
+    M.rg_code = (unsigned*)flag(28); M.rg_R = t[29]; M.rg_ng = t[30]; M.rg_words = t[31];
+    const CsrPlan p = plan_csr(M, op, windowed || g_tune.split_rows > 0, want_partials != 0);
+    const int out[11] = {(int)p.kernel, p.family, p.tile_rows, p.bpc, p.xcd_map, p.tpp, p.nt, p.ja16, p.jbase, p.fused_zr, kernel_family(M, nullptr)};
+    std::copy(out, out + 11, plan);
+    if (bytes) *bytes = p.bytes;
+    return FASP_SUCCESS;
+}
+
+// CPU test entry: the row-group coding of A as an upload would build it (device_csr.hip.h, build_rgroup), decoded again and walked on the host
+int fasp_hip_rgroup_selftest(const dCSRmat* A, int rows_per_group, int waves, double min_reuse, int* info, double* bytes, int* ia_out, int* ja_out, double* val_out, const double* x, double* y)
+{
+    if (!A || !info || A->row < 0 || A->nnz < 0 || (rows_per_group != 8 && rows_per_group != 16) || (waves != 2 && waves != 4 && waves != 8)) return ERROR_INPUT_PAR;
+    HostCSR M;
+    M.row = A->row; M.col = A->col; M.nnz = A->nnz;
+    M.ia.view(A->IA, (size_t)A->row + 1); M.ja.view(A->JA, (size_t)std::max(A->nnz, 1)); M.val.view(A->val, (size_t)std::max(A->nnz, 1));
+    RGroupHost G;
+    int why = 0;
+    const bool ok = build_rgroup(M, rows_per_group, min_reuse > 0.0 ? min_reuse : RG_MIN_REUSE, G, &why);
+    unsigned long long hsh = 1469598103934665603ull;   // FNV-1a over table, code and values
+    auto eat = [&](const void* p, size_t n) { const unsigned char* q = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { hsh ^= q[i]; hsh *= 1099511628211ull; } };
+    if (ok) { eat(G.meta.data(), 4 * G.meta.size()); eat(G.code.data(), 4 * (size_t)(((G.words + 3) & ~3ll) + 4)); eat(G.val.data(), 8 * ((size_t)M.nnz + 2)); }
+    info[0] = ok ? 1 : 0; info[1] = why; info[2] = G.R; info[3] = G.ng; info[4] = (int)G.chunks; info[5] = (int)G.ucols; info[6] = (int)G.words;
+    info[7] = (int)(hsh & 0x7fffffffu); info[8] = (int)((hsh >> 32) & 0x7fffffffu); info[9] = RG_MIN_ROW;
+    if (bytes) *bytes = ok ? rgroup_bytes(M.nnz, G.words, G.ng) : 0.0;
+    if (!ok) return FASP_SUCCESS;
+    if (ia_out && ja_out && val_out) rgroup_decode_host(G, M.row, ia_out, ja_out, val_out);
+    if (x && y) rgroup_mxv_host(G, M.row, waves, x, y);
     return FASP_SUCCESS;
 }
 
@@ -2528,6 +2576,7 @@ int fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double* 
     {
         HostThreads team;
         st = upload_csr(M, D.A);
+        if (st >= 0) st = upload_rgroup(M, D.A);
         if (st >= 0 && M.row == M.col) st = upload_diag(M, D);
     }
     if (st >= 0 && (op == 5 || op == 6) && !D.diag) st = ERROR_INPUT_PAR;
@@ -2551,6 +2600,7 @@ int fasp_hip_matrix_traits(const dCSRmat* A, int* traits)
     {
         HostThreads team;
         st = upload_csr(M, D.A);
+        if (st >= 0) st = upload_rgroup(M, D.A);
         if (st >= 0 && M.row == M.col) st = upload_diag(M, D);
     }
     if (st >= 0) {
@@ -2559,6 +2609,34 @@ int fasp_hip_matrix_traits(const dCSRmat* A, int* traits)
                              (int)d.sell_slots, (int)d.ntcols, d.es_W, d.es_nc, d.code != nullptr, d.pat != nullptr, d.rowbase != nullptr, d.dpos != nullptr,
                              d.dup_diag, d.ja16 != nullptr, d.jbase != nullptr, d.lja16 != nullptr, d.sell_code != nullptr, d.es_tab != nullptr, d.es_ja16 != nullptr};
         std::copy(out, out + 28, traits);
+    }
+    free_level(D);
+    return st < 0 ? st : FASP_SUCCESS;
+}
+
+// ... and the 32 traits of fasp_hip_csr_plan2's layout (the row-group copy behind the 28), under the tune keys in force at the call
+int fasp_hip_matrix_traits2(const dCSRmat* A, int* traits)
+{
+    FASP_ENTRY();
+    if (!A || !traits || ctx_init() < 0) return ERROR_INPUT_PAR;
+    HostCSR M;
+    M.row = A->row; M.col = A->col; M.nnz = A->nnz;
+    M.ia.view(A->IA, (size_t)A->row + 1); M.ja.view(A->JA, (size_t)std::max(A->nnz, 1)); M.val.view(A->val, (size_t)std::max(A->nnz, 1));
+    DevLevel D;
+    int st;
+    {
+        HostThreads team;
+        st = upload_csr(M, D.A);
+        if (st >= 0) st = upload_rgroup(M, D.A);
+        if (st >= 0 && M.row == M.col) st = upload_diag(M, D);
+    }
+    if (st >= 0) {
+        const DevCSR& d = D.A;
+        const int out[32] = {d.row, d.col, d.nnz, d.kind, d.lanes, d.wrows, d.wcap, d.nxrows, d.plane, d.npat, d.npent, d.sell_nv, d.sell_nslice,
+                             (int)d.sell_slots, (int)d.ntcols, d.es_W, d.es_nc, d.code != nullptr, d.pat != nullptr, d.rowbase != nullptr, d.dpos != nullptr,
+                             d.dup_diag, d.ja16 != nullptr, d.jbase != nullptr, d.lja16 != nullptr, d.sell_code != nullptr, d.es_tab != nullptr, d.es_ja16 != nullptr,
+                             d.rg_code != nullptr, d.rg_R, d.rg_ng, (int)d.rg_words};
+        std::copy(out, out + 32, traits);
     }
     free_level(D);
     return st < 0 ? st : FASP_SUCCESS;
@@ -2579,7 +2657,7 @@ double fasp_hip_time_matrix(const dCSRmat* A, int op, int reps, int* kind_out)
     DevCSR D;
     {
         HostThreads team;
-        if (upload_csr(M, D) < 0) { D.release(); return -1.0; }
+        if (upload_csr(M, D) < 0 || upload_rgroup(M, D) < 0) { D.release(); return -1.0; }
     }
     const int n = A->row, nc = A->col;
     double *x = nullptr, *y = nullptr, *w = nullptr, *dg = nullptr;

@@ -81,7 +81,10 @@ double fasp_hip_rap_time(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, i
  *     kernels, 1, 2 = default), compress (lossless matrix coding on/off), ja16, ws2_bpc, rpl, lds_tab, xcd_pat, rp_strip (coded operators
  *     of a 3-D grid: an XCD sweeps a strip of every grid plane -- 1: the square operators, 2 (default): the transfer operators too -- or,
  *     0, a slab of planes), estream (k_csr_estream, the entry-parallel kernel of long-row operators: 1 (default) = where it measured
- *     faster -- mean rows of fewer than 256 entries --, 2 = wherever its tables exist, 0 = the row kernels);
+ *     faster -- mean rows of fewer than 256 entries --, 2 = wherever its tables exist, 0 = the row kernels), rgroup (k_csr_rgroup, groups of
+ *     consecutive rows of a long-row square operator over the union of their columns: 1 (default) = where it measured faster, and not
+ *     under estream 0; 2 = wherever the copy exists; 0 = never, and no copy is built at upload), rgroup_rows (8 (default) or 16 rows per
+ *     group; read at upload), rgroup_waves (2, 4 or 8 waves per group; otherwise by the mean row length);
  *   coarse solve: spcg_persist, spcg_fused, spcg_batch, spcg_grid, small_lds, small_onewave (coarsest levels of <= 128
  *     rows: 4 (default) = matrix in registers as 16 x 16 blocks, the direction broadcast inside the multiply-adds, the next
  *     direction sent before the tests of the iteration (k_spcg_dpp<.., true>); 3 = the same without sending ahead; 2 = matrix
@@ -193,6 +196,21 @@ int  fasp_hip_matrix_op(const dCSRmat* A, int op, const double* x, const double*
 /* test entry: the 28 traits of fasp_hip_csr_plan's layout read from the device copy fasp_hip_matrix_op makes of A (the same upload; the diagonal
  * tables for a square matrix), which is freed again: with them fasp_hip_csr_plan names the kernel of every operation on that copy. */
 int  fasp_hip_matrix_traits(const dCSRmat* A, int* traits);
+/* fasp_hip_csr_plan with the traits of the row-group copy (csrc/kernels5.hip.h) behind the 28: traits (32 ints) = {the 28 of fasp_hip_csr_plan, then
+ * rg_code set (0 / 1), rows per group, groups, 32-bit words of code}.  fasp_hip_csr_plan itself is unchanged: through it the copy counts as
+ * absent.  Kernel codes beyond its 0 .. 28: 29 .. 34 k_csr_rgroup<R, NW> (16, 4), (16, 8), (8, 4), (8, 8), (16, 2), (8, 2) -- family 0, like k_csr_estream; *bytes =
+ * the coded form's 8 per entry + 4 per word + 16 per group.  fasp_hip_matrix_traits2: those 32 traits of the device copy
+ * fasp_hip_matrix_op makes of A under the tune keys in force ("rgroup" 0: no copy is built). */
+int  fasp_hip_csr_plan2(const int* traits, int op, int windowed, int want_partials, int* plan, double* bytes);
+int  fasp_hip_matrix_traits2(const dCSRmat* A, int* traits);
+/* The row-group coding of k_csr_rgroup (csrc/kernels5.hip.h) built on the HOST as an upload would build it.  rows_per_group: 8 or 16; waves: 2, 4 or
+ * 8 (the waves per group of the walk); min_reuse: smallest entries / union columns accepted (<= 0: the product's 3.0).  info[10] = {coded (1 / 0),
+ * why not (0 coded, 1 not square, 2 mean row shorter than 128 entries, 3 a group's columns span more than 65 535, 4 a row holds a column twice,
+ * 5 reuse below the bound), rows per group, groups, chunks of 64 union columns, union columns, 32-bit words of code, two halves (31 bits each) of a
+ * hash over table, code and values, the mean-row bound}; *bytes = what one pass over the coded form reads.  When coded and the pointers are
+ * given: ia_out / ja_out / val_out = the form decoded back to CSR with every row sorted by column (sized like A's arrays), y = A x over the coded
+ * form in the kernel's order (per wave its chunks, the 64 lanes by the DPP tree, the waves in order).  No GPU needed. */
+int  fasp_hip_rgroup_selftest(const dCSRmat* A, int rows_per_group, int waves, double min_reuse, int* info, double* bytes, int* ia_out, int* ja_out, double* val_out, const double* x, double* y);
 /* test entry: ONE sequential block sweep of the host matrix A (square, storage_manner 0, 1 <= nb <= 7, a diagonal block in every row) on the
  * device, through the level schedule and the per-level launches the block AMG cycle smooths with: block Gauss-Seidel (sor = 0; w unused) or
  * block SOR with weight w, rows ascending (descend = 0) or descending, u updated in place.  diaginv: the ROW inverse diagonal blocks
