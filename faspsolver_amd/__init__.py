@@ -76,6 +76,12 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_dcsr_swz_backward", "fasp_precond_swz", "fasp_swz_data_free", "fasp_solver_dcsr_krylov_swz",
     "fasp_hip_csr_swz_levels", "fasp_hip_csr_swz", "fasp_hip_csr_swz_resident_count", "fasp_hip_time_csr_swz",
     "fasp_hip_csr_swz_runs", "fasp_hip_amg_get_swz", "fasp_hip_amg_swz_info", "fasp_hip_amg_swz_sweep_time", "fasp_hip_amg_swz_levels",
+    "fasp_smoother_dbsr_jacobi", "fasp_smoother_dbsr_jacobi_setup", "fasp_smoother_dbsr_gs", "fasp_smoother_dbsr_gs1",
+    "fasp_smoother_dbsr_gs_ascend", "fasp_smoother_dbsr_gs_ascend1", "fasp_smoother_dbsr_gs_descend", "fasp_smoother_dbsr_gs_descend1",
+    "fasp_smoother_dbsr_gs_order1", "fasp_smoother_dbsr_gs_order2", "fasp_smoother_dbsr_sor", "fasp_smoother_dbsr_sor1",
+    "fasp_smoother_dbsr_sor_ascend", "fasp_smoother_dbsr_sor_descend", "fasp_smoother_dbsr_sor_order",
+    "fasp_hip_bsr_smoother_create", "fasp_hip_bsr_smoother_apply", "fasp_hip_bsr_smoother_destroy",
+    "fasp_hip_bsr_smoother_info", "fasp_hip_bsr_sweep_plan", "fasp_hip_bsr_sweep_time",
 ]
 
 
@@ -230,6 +236,24 @@ def lib():
     L.fasp_hip_dist_level_info.argtypes = [C.c_void_p, C.c_int, T.c_int_p]
     L.fasp_hip_dist_get_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, P(T.dCSRmat)]
     L.fasp_hip_dist_get_list.argtypes = [C.c_void_p, C.c_int, C.c_int, P(T.ivector)]
+    # the block smoothers (ItrSmootherBSR.c) and the resident handle
+    M, V, D, I = P(T.dBSRmat), P(T.dvector), T.c_double_p, T.c_int_p
+    for name, args in (
+            ("jacobi", [M, V, V]), ("jacobi_setup", [M, D]), ("gs", [M, V, V, C.c_int, I]), ("gs1", [M, V, V, C.c_int, I, D]),
+            ("gs_ascend", [M, V, V, D]), ("gs_ascend1", [M, V, V]), ("gs_descend", [M, V, V, D]), ("gs_descend1", [M, V, V]),
+            ("gs_order1", [M, V, V, D, I]), ("gs_order2", [M, V, V, I, D]), ("sor", [M, V, V, C.c_int, I, C.c_double]),
+            ("sor1", [M, V, V, C.c_int, I, D, C.c_double]), ("sor_ascend", [M, V, V, D, C.c_double]),
+            ("sor_descend", [M, V, V, D, C.c_double]), ("sor_order", [M, V, V, D, I, C.c_double])):
+        f = getattr(L, "fasp_smoother_dbsr_" + name)
+        f.argtypes, f.restype = args, None
+    L.fasp_hip_bsr_smoother_create.argtypes = [P(C.c_void_p), M, D, C.c_int, I]
+    L.fasp_hip_bsr_smoother_apply.argtypes = [C.c_void_p, C.c_int, C.c_double, V, V]
+    L.fasp_hip_bsr_smoother_destroy.argtypes = [C.c_void_p]
+    L.fasp_hip_bsr_smoother_destroy.restype = None
+    L.fasp_hip_bsr_smoother_info.argtypes = [C.c_void_p, D]
+    L.fasp_hip_bsr_sweep_plan.argtypes = [M, C.c_int, I, P(C.c_longlong), I, I, I, I, P(C.c_longlong), I]
+    L.fasp_hip_bsr_sweep_time.argtypes = [M, C.c_int, I, C.c_int, C.c_double, C.c_int, C.c_int, D]
+    L.fasp_hip_bsr_sweep_time.restype = C.c_double
     _lib = L
     # ILU preconditioner (csrc/ilu_setup.cpp, csrc/ilu.hip.h)
     L.fasp_param_ilu_init.argtypes = [P(T.ILU_param)]
@@ -841,6 +865,81 @@ class BSRAMG:
     def free(self):
         if self.h:
             lib().fasp_hip_bsr_amg_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+BSR_SWEEP_GS, BSR_SWEEP_SOR, BSR_SWEEP_IDENTITY = 0, 1, 2   # `kind` of fasp_hip_bsr_smoother_apply
+
+
+def _mark_p(mark):
+    if mark is None:
+        return None, None
+    m = np.ascontiguousarray(mark, dtype=np.int32)
+    return m.ctypes.data_as(T.c_int_p), m
+
+
+def bsr_sweep_plan(ia, ja, nb, order=T.ASCEND, mark=None):
+    """fasp_hip_bsr_sweep_plan (host only): the slab plan of a block sweep as a dict, or None when nothing is swept.
+    Raises ValueError(status) for a refused matrix or mark."""
+    ia = np.ascontiguousarray(ia, dtype=np.int32); ja = np.ascontiguousarray(ja, dtype=np.int32)
+    n = len(ia) - 1
+    A = T.dBSRmat(n, n, int(ia[-1]), nb, 0, None, ia.ctypes.data_as(T.c_int_p), ja.ctypes.data_as(T.c_int_p))
+    mp, _m = _mark_p(mark)
+    info = (C.c_longlong * 6)()
+    st = lib().fasp_hip_bsr_sweep_plan(C.byref(A), order, mp, info, None, None, None, None, None, None)
+    if st < 0:
+        raise ValueError(st)
+    if st == 1:
+        return None
+    nlev, nchunk, nent = int(info[0]), int(info[1]), int(info[2])
+    level = np.zeros(max(n, 1), dtype=np.int32); lvl_chunk = np.zeros(nlev + 1, dtype=np.int32)
+    rows = np.zeros(max(64 * nchunk, 1), dtype=np.int32); ln = np.zeros(max(64 * nchunk, 1), dtype=np.int32)
+    cbase = np.zeros(max(nchunk, 1), dtype=np.int64); cols = np.zeros(max(nent, 1), dtype=np.int32)
+    ip = lambda a: a.ctypes.data_as(T.c_int_p)
+    st = lib().fasp_hip_bsr_sweep_plan(C.byref(A), order, mp, info, ip(level), ip(lvl_chunk), ip(rows), ip(ln),
+                                       cbase.ctypes.data_as(C.POINTER(C.c_longlong)), ip(cols))
+    assert st == 0, st
+    return dict(levels=nlev, chunks=nchunk, nent=nent, nreal=int(info[3]), maxlen=int(info[4]), level=level[:n], lvl_chunk=lvl_chunk,
+                rows=rows[:64 * nchunk], len=ln[:64 * nchunk], cbase=cbase[:nchunk], cols=cols[:nent])
+
+
+class BSRSmoother:
+    """Resident block smoother (fasp_hip_bsr_smoother): the sweep plan of (A, order, mark) uploaded once, one sweep per apply().
+    diaginv=None: the inverse diagonal blocks are computed as fasp_smoother_dbsr_gs computes them."""
+
+    def __init__(self, ia, ja, val, nb, order=T.ASCEND, mark=None, diaginv=None):
+        A, _keep = T.as_bsr(ia, ja, val, nb)
+        mp, _m = _mark_p(mark)
+        d = None if diaginv is None else np.ascontiguousarray(diaginv, dtype=np.float64)
+        self.h = C.c_void_p()
+        self.status = lib().fasp_hip_bsr_smoother_create(C.byref(self.h), C.byref(A), None if d is None else T.dp(d), order, mp)
+        if self.status < 0:
+            self.h = C.c_void_p()
+            raise RuntimeError(f"fasp_hip_bsr_smoother_create failed with status {self.status}")
+        self.n = A.ROW * nb
+
+    def apply(self, b, u, kind=BSR_SWEEP_GS, weight=1.0):
+        """One sweep: u (float64, contiguous) is the iterate on entry and on exit.  Returns the status."""
+        bv, _b = T.as_vec(b)
+        assert u.dtype == np.float64 and u.flags.c_contiguous
+        uv = T.dvector(len(u), T.dp(u))
+        return lib().fasp_hip_bsr_smoother_apply(self.h, kind, weight, C.byref(bv), C.byref(uv))
+
+    def info(self):
+        """{levels, chunks, slab entries, padded entries, form of the last apply, form an apply would take now}"""
+        out = np.zeros(6)
+        lib().fasp_hip_bsr_smoother_info(self.h, T.dp(out))
+        return dict(levels=int(out[0]), chunks=int(out[1]), nent=int(out[2]), padded=int(out[3]), last_form=int(out[4]), auto_form=int(out[5]))
+
+    def free(self):
+        if self.h:
+            lib().fasp_hip_bsr_smoother_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -14,6 +14,7 @@ c_double_p = C.POINTER(C.c_double)
 # --- constants (fasp_const.h) -------------------------------------------------
 FASP_SUCCESS = 0
 ERROR_INPUT_PAR = -13
+ERROR_NUM_BLOCKS = -18
 ERROR_MISC = -19
 ERROR_ALLOC_MEM = -20
 ERROR_AMG_INTERP_TYPE = -30

@@ -62,6 +62,7 @@ namespace {
 struct IluDev;
 void    ilu_dev_destroy(IluDev* D);
 IluDev* ilu_upload(const ILU_data* d, int nb, int* st);
+struct BsrSweepDev;   // bsr_sweep.hip.h: the device copy of the slab plan of a sweep direction
 }  // namespace
 struct BsrLevel {
     std::unique_ptr<TmpBSR> A, P, R;
@@ -70,6 +71,7 @@ struct BsrLevel {
     int  n = 0;  // scalar rows (owned)
     bool x_zero = false;
     DevLevel::Sched sched[2];  // level schedules of the sequential block sweeps: 0 ascending, 1 descending
+    BsrSweepDev* sweep[2] = {nullptr, nullptr};   // fasp_hip_tune("bsr_cycle_sweep", 1): their slab plans instead (bsr_sweep.hip.h)
     // row partition (one process per GPU; single GPU: replicated, nv == n): owned block rows [row0, row0 + nloc) of
     // nglobal, vectors of nv = (nloc + ghost blocks) * nb scalars, halo lists in SCALAR indices (a block = nb entries)
     bool replicated = true;
@@ -168,8 +170,11 @@ static int bsr_seq_launch(const TmpBSR& M, const DevLevel::Sched& S, const doubl
 
 // One sequential block sweep (Gauss-Seidel or SOR, ascending or descending) as level-scheduled launches:
 // the rows of a dependency level are mutually uncoupled, so the result is the sequential sweep.
+static int bsr_cycle_sweep(fasp_hip_amg_bsr* h, int level, bool descend, bool sor, double w);   // bsr_sweep.hip.h
+void bsr_level_sweeps_destroy(BsrLevel& Lv);                                                     // ... frees Lv.sweep
 static int bsr_seq_sweep(fasp_hip_amg_bsr* h, int level, bool descend, bool sor, double w)
 {
+    if (g_tune.bsr_cycle_sweep) return bsr_cycle_sweep(h, level, descend, sor, w);   // the slab plan and kernels: same bits
     BsrLevel& Lv = h->L[level];
     DevLevel::Sched& S = Lv.sched[descend ? 1 : 0];
     if (!S.built) {

@@ -40,6 +40,7 @@
 
 #include "fasp_comm.h"
 #include "fasp_internal.h"
+#include "bsr_sweep_plan.h"
 #include "krylov_ws.h"
 #include "kernels.hip.h"
 #include "kernels2.hip.h"
@@ -933,6 +934,7 @@ void fasp_hip_bsr_amg_destroy(fasp_hip_amg_bsr* h)
         if (Lv.d_send_idx) (void)hipFree(Lv.d_send_idx);
         if (Lv.d_sendbuf) (void)hipFree(Lv.d_sendbuf);
         ilu_dev_destroy(Lv.ilu);
+        bsr_level_sweeps_destroy(Lv);
     }
     double* v[] = {h->b, h->u, h->p, h->t, h->r};
     for (double* q : v) if (q) (void)hipFree(q);
@@ -1202,6 +1204,7 @@ precond* fasp_hip_precond_setup(dCSRmat* A, AMG_param* amgparam)
 
 #include "precond_api.hip.h"
 #include "ilu.hip.h"
+#include "bsr_sweep.hip.h"
 #include "rap.hip.h"
 
 void fasp_hip_precond_free(precond* pc)
@@ -2251,6 +2254,8 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "swz_run")) g_tune.swz_run = value;   // Schwarz sweeps: stretches of narrow dependency levels in one launch of one workgroup (k_csr_swz_run): -1 (default) inside the AMG cycles on the levels whose schedule is nearly serial (csr_swz.hip.h, SWZ_RUN_MEAN), 0 never, 1 on every Schwarz level of a cycle and in the stand-alone entries -- same bits
     else if (!std::strcmp(key, "swz_run_width")) g_tune.swz_run_width = value;   // blocks a level of such a stretch has at most (16); read at launch
     else if (!std::strcmp(key, "ilu_form")) g_tune.ilu_form = value;   // ILU triangular solves: -1 (default) by the schedule's depth, 0 one launch per level, 1 one launch
+    else if (!std::strcmp(key, "bsr_sweep_form")) g_tune.bsr_sweep_form = value;   // block GS / SOR sweeps over the slab plan (bsr_sweep.hip.h): -1 (default) by the plan's depth, 0 one launch per level, 1 one launch -- same bits
+    else if (!std::strcmp(key, "bsr_cycle_sweep")) g_tune.bsr_cycle_sweep = value;   // GS / SGS / SOR / SSOR sweeps of the block AMG cycle and the GS sweeps behind its ILU step: 0 (default) k_bsr_seq_level per dependency level, 1 the slab plan and kernels of bsr_sweep.hip.h -- same bits
     else if (!std::strcmp(key, "str_ilu_form")) g_tune.str_ilu_form = value;   // structured ILU solves (str_ilu_plan): -1 (default) by the plan, 0 one launch per level, 1 planes pipelined over workgroups (3-D)
     else if (!std::strcmp(key, "str_ilu_wgs")) g_tune.str_ilu_wgs = value;     // workgroups of the pipelined form at most (0, default: twice the compute units)
     else if (!std::strcmp(key, "str_sweep_form")) g_tune.str_sweep_form = value;   // structured GS / SOR sweeps (str_sweep_plan): -1 (default) by the plan, 0 one launch per level, 1 planes pipelined over workgroups (3-D), 2 the ordered form (level list)

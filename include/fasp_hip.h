@@ -47,6 +47,7 @@ extern "C" {
 #define ERROR_WRONG_FILE      (-11)
 #define ERROR_INPUT_PAR       (-13)
 #define ERROR_MAT_SIZE        (-15)
+#define ERROR_NUM_BLOCKS      (-18)
 #define ERROR_MISC            (-19)
 #define ERROR_ALLOC_MEM       (-20)
 #define ERROR_DATA_STRUCTURE  (-21)
@@ -869,6 +870,43 @@ void  fasp_smoother_dbsr_ilu(dBSRmat* A, dvector* b, dvector* x, void* data);   
 /* SolWrapper.c:326: ILUk(0)-preconditioned VFGMRES on a caller's BSR arrays (Fortran calling convention) */
 void  fasp_fwrapper_dbsr_krylov_ilu_(int* n, int* nnz, int* nb, int* ia, int* ja, double* a, double* b, double* u,
                                      double* tol, int* maxit, int* ptrlvl);
+
+/* The block (BSR) smoothers (ItrSmootherBSR.c): one sweep on the device, host vectors of ROW*nb, with the reference's
+ * result bit for bit.  Orders, as _gs1 / _sor1 dispatch them: a non-NULL mark wins -- it is the visiting sequence, a permutation of
+ * 0 .. ROW-1 --, else ASCEND or DESCEND; mark == NULL with any other order does nothing.  _jacobi, _gs and _sor invert the diagonal blocks on
+ * the host (fasp_smat_inv; 1.0 / d for nb = 1; the last diagonal block a row stores counts), the others take them as diaginv; the entries
+ * ending in 1 (_gs_ascend1, _gs_descend1) and _gs_order2 assume identity diagonal blocks (`work` is not used).  Off-diagonal entries are
+ * taken in storage order, columns need not be sorted, rows may be empty.  A: square, storage_manner 0.  Every entry is create + apply +
+ * destroy of the handle below.  Ends the process with a message: nb outside 1 .. 7 (ERROR_NUM_BLOCKS), a mark that is not a permutation,
+ * ROW != COL, a b or u shorter than ROW*nb, a NULL argument (ERROR_INPUT_PAR), no usable device (ERROR_MISC: there is no CPU fallback).
+ * fasp_smoother_dbsr_jacobi_setup is host code. */
+void fasp_smoother_dbsr_jacobi(dBSRmat* A, dvector* b, dvector* u);                                                  /* ItrSmootherBSR.c:59 */
+void fasp_smoother_dbsr_jacobi_setup(dBSRmat* A, double* diaginv);                                                   /* ItrSmootherBSR.c:163 */
+void fasp_smoother_dbsr_gs(dBSRmat* A, dvector* b, dvector* u, int order, int* mark);                                /* ItrSmootherBSR.c:410 */
+void fasp_smoother_dbsr_gs1(dBSRmat* A, dvector* b, dvector* u, int order, int* mark, double* diaginv);              /* ItrSmootherBSR.c:520 */
+void fasp_smoother_dbsr_gs_ascend(dBSRmat* A, dvector* b, dvector* u, double* diaginv);                              /* ItrSmootherBSR.c:552 */
+void fasp_smoother_dbsr_gs_ascend1(dBSRmat* A, dvector* b, dvector* u);                                              /* ItrSmootherBSR.c:619 */
+void fasp_smoother_dbsr_gs_descend(dBSRmat* A, dvector* b, dvector* u, double* diaginv);                             /* ItrSmootherBSR.c:683 */
+void fasp_smoother_dbsr_gs_descend1(dBSRmat* A, dvector* b, dvector* u);                                             /* ItrSmootherBSR.c:751 */
+void fasp_smoother_dbsr_gs_order1(dBSRmat* A, dvector* b, dvector* u, double* diaginv, int* mark);                   /* ItrSmootherBSR.c:816 */
+void fasp_smoother_dbsr_gs_order2(dBSRmat* A, dvector* b, dvector* u, int* mark, double* work);                      /* ItrSmootherBSR.c:888 */
+void fasp_smoother_dbsr_sor(dBSRmat* A, dvector* b, dvector* u, int order, int* mark, double weight);                /* ItrSmootherBSR.c:959 */
+void fasp_smoother_dbsr_sor1(dBSRmat* A, dvector* b, dvector* u, int order, int* mark, double* diaginv, double weight);   /* ItrSmootherBSR.c:1075 */
+void fasp_smoother_dbsr_sor_ascend(dBSRmat* A, dvector* b, dvector* u, double* diaginv, double weight);              /* ItrSmootherBSR.c:1115 */
+void fasp_smoother_dbsr_sor_descend(dBSRmat* A, dvector* b, dvector* u, double* diaginv, double weight);             /* ItrSmootherBSR.c:1234 */
+void fasp_smoother_dbsr_sor_order(dBSRmat* A, dvector* b, dvector* u, double* diaginv, int* mark, double weight);    /* ItrSmootherBSR.c:1358 */
+/* The resident form for a caller that smooths with one matrix many times (a precond.fct callback): the sweep plan of
+ * (A, order, mark) is built and uploaded once.  fasp_hip_bsr_smoother_create: diaginv = the ROW inverse diagonal blocks, or NULL to have them
+ * computed as _gs does; returns FASP_SUCCESS, ERROR_NUM_BLOCKS (nb outside 1 .. 7), ERROR_INPUT_PAR (a NULL pointer, ROW != COL, storage_manner
+ * != 0, a mark that is not a permutation), ERROR_DATA_STRUCTURE (IA / JA inconsistent), ERROR_MISC (no device), ERROR_ALLOC_MEM; *h is NULL
+ * unless it succeeds.  The checks come before any device work.  A is not needed after the call.  fasp_hip_bsr_smoother_apply: one sweep,
+ * u = sweep(b, u) on host vectors; kind 0 Gauss-Seidel, 1 SOR with `weight`, 2 the identity-diagonal form; ERROR_INPUT_PAR for a b or u
+ * shorter than ROW*nb or another kind; ERROR_MISC for a device failure.  A handle of (mark NULL, order neither ASCEND nor DESCEND) sweeps
+ * nothing. */
+typedef struct fasp_hip_bsr_smoother fasp_hip_bsr_smoother;
+int  fasp_hip_bsr_smoother_create(fasp_hip_bsr_smoother** h, const dBSRmat* A, const double* diaginv, int order, const int* mark);
+int  fasp_hip_bsr_smoother_apply(fasp_hip_bsr_smoother* h, int kind, double weight, const dvector* b, dvector* u);
+void fasp_hip_bsr_smoother_destroy(fasp_hip_bsr_smoother* h);
 
 /* The overlapping (multiplicative) Schwarz method of a CSR matrix.  The host side needs no GPU and leaves the
  * reference's arrays, entry order included: fasp_dcsr_sympart (1.0 A + 0.0 A^T: the symmetrised pattern with A's values), fasp_dcsr_shift,

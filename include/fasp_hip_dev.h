@@ -114,6 +114,11 @@ double fasp_hip_rap_time(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, i
  *     deeper than 24 levels, else one launch per level; 0 always one launch per level; 1 always one launch) -- same bits;
  *     ilu_smooth_fused (the ILU step of the block AMG cycle: 1 (default) the U solve writes x = x + z itself, 0 a separate
  *     axpy pass) -- same bits;
+ *   block sweeps: bsr_sweep_form (the Gauss-Seidel / SOR sweeps of fasp_smoother_dbsr_gs and its kin and of the fasp_hip_bsr_smoother
+ *     handle: -1 (default) one launch for plans deeper than 64 levels of at most 8 chunks of 64 block rows on average, else one launch
+ *     per level; 0 / 1 force either), bsr_cycle_sweep
+ *     (the Gauss-Seidel / SOR sweeps of the block AMG cycle: 0 (default) k_bsr_seq_level per dependency level, 1 the slab plan and
+ *     kernels of csrc/bsr_sweep.hip.h) -- same bits;
  *   multi-GPU: halo_overlap (exchange beside the interior rows, default 1), split_rows (test mode: every operator in
  *     three row windows), seq_partition (set before the upload, or FASP_HIP_SEQ_PARTITION=1: hierarchies with Gauss-Seidel / SOR
  *     smoothers are row-partitioned too and the ranks sweep by turns; default 0: such hierarchies keep every level whole),
@@ -318,6 +323,29 @@ int    fasp_hip_amg_get_swz(const fasp_hip_amg* h, int level, SWZ_data* view);
 int    fasp_hip_amg_swz_levels(const fasp_hip_amg* h, int level, int* swz_levels);
 int    fasp_hip_amg_swz_info(const fasp_hip_amg* h, int level, int* info);
 double fasp_hip_amg_swz_sweep_time(fasp_hip_amg* h, int level, int dir, int reps);
+/* The block sweeps over the slab plan (csrc/bsr_sweep.hip.h, csrc/bsr_sweep_plan.h).
+ * fasp_hip_bsr_smoother_info: info (6 doubles) = {dependency levels, chunks of 64 block rows, slab entries, padded slab entries, form of the
+ * last apply (-1 none yet, 0 one launch per level, 1 one launch), form an apply would take now under fasp_hip_tune("bsr_sweep_form", ..)};
+ * returns 1, or 0 for a handle that sweeps nothing.
+ * fasp_hip_bsr_sweep_plan (pure host code): the plan of (A, order, mark).  info (6) = {levels, chunks, slab entries, actual off-diagonal
+ * entries, longest row, ROW}; the arrays, each may be NULL (call once with NULLs for the sizes): level[ROW], lvl_chunk[levels + 1] (first
+ * chunk of each level), rows[64 chunks] (block row of a slot, -1: padding), len[64 chunks] (off-diagonal entries of the slot's row),
+ * cbase[chunks] (first slab entry of a chunk), cols[slab entries] (entry k of slot (c, lane) at cbase[c] + 64 k + lane: the column, bit 31
+ * set when the entry reads u_new, -1: padding).  Returns 0, 1 when nothing is swept, ERROR_NUM_BLOCKS / ERROR_INPUT_PAR /
+ * ERROR_DATA_STRUCTURE as fasp_hip_bsr_smoother_create.
+ * fasp_hip_bsr_sweep_time: microseconds per sweep over `reps` back-to-back sweeps after one warm-up (b_i = u_i = sin(0.37 i) + 0.1, inverse
+ * blocks computed on the host; kind as fasp_hip_bsr_smoother_apply).  form: 0 the per-level launches of k_bsr_seq_level the block AMG cycle
+ * takes by default (ascending / descending Gauss-Seidel and SOR only), 1 the slab plan with one launch per level, 2 the slab plan in one
+ * launch, -1 the slab plan in the form fasp_hip_tune("bsr_sweep_form", ..) selects.  info (8 doubles, may be NULL) = {levels, chunks, slab
+ * entries, actual entries, form taken (0, 1, 2 as above), bytes one sweep moves at least, milliseconds of plan creation (schedule or plan +
+ * upload), longest row}.  < 0: refused or no device.
+ * Tune keys: bsr_sweep_form (-1 default: one launch for plans deeper than 64 levels with at most 8 chunks per level on average, else one
+ * per level; 0 / 1 force a form), bsr_cycle_sweep (1: the
+ * Gauss-Seidel / SOR sweeps of the block AMG cycle take the slab plan; 0, default: k_bsr_seq_level) -- same bits. */
+int    fasp_hip_bsr_smoother_info(const fasp_hip_bsr_smoother* h, double info[6]);
+int    fasp_hip_bsr_sweep_plan(const dBSRmat* A, int order, const int* mark, long long info[6], int* level, int* lvl_chunk, int* rows, int* len,
+                               long long* cbase, int* cols);
+double fasp_hip_bsr_sweep_time(const dBSRmat* A, int order, const int* mark, int kind, double weight, int form, int reps, double* info);
 /* one-rank exercise of every RCCL call the transport makes (0 = all results correct) */
 int  fasp_hip_comm_selftest(void);
 
