@@ -82,7 +82,13 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_smoother_dbsr_sor_ascend", "fasp_smoother_dbsr_sor_descend", "fasp_smoother_dbsr_sor_order",
     "fasp_hip_bsr_smoother_create", "fasp_hip_bsr_smoother_apply", "fasp_hip_bsr_smoother_destroy",
     "fasp_hip_bsr_smoother_info", "fasp_hip_bsr_sweep_plan", "fasp_hip_bsr_sweep_time",
+    "fasp_solver_dcsr_spcg", "fasp_solver_dcsr_spbcgs", "fasp_solver_dcsr_spminres", "fasp_solver_dcsr_spgmres", "fasp_solver_dcsr_spvgmres",
+    "fasp_solver_dcsr_itsolver_s", "fasp_solver_dcsr_krylov_s", "fasp_solver_dbsr_spbcgs", "fasp_solver_dbsr_spgmres",
+    "fasp_solver_dbsr_spvgmres", "fasp_solver_dstr_spcg", "fasp_solver_dstr_spbcgs", "fasp_solver_dstr_spminres",
+    "fasp_solver_dstr_spgmres", "fasp_solver_dstr_spvgmres", "fasp_hip_safe_update_selftest", "fasp_hip_plugin_solve_seconds",
 ]
+SAFE_METHODS = ("spcg", "spbcgs", "spminres", "spgmres", "spvgmres")   # the safe-net Krylov methods (KrySP*.c) ...
+SAFE_FORMATS = {"csr": SAFE_METHODS, "bsr": ("spbcgs", "spgmres", "spvgmres"), "str": SAFE_METHODS}   # ... the reference has per format
 
 
 def build(verbose=False):
@@ -410,6 +416,15 @@ def lib():
     L.fasp_hip_amg_swz_levels.argtypes = [C.c_void_p, C.c_int, P(C.c_int)]
     L.fasp_hip_amg_swz_sweep_time.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.fasp_hip_amg_swz_sweep_time.restype = C.c_double
+    for fmt, mat in (("csr", T.dCSRmat), ("bsr", T.dBSRmat), ("str", T.dSTRmat)):   # the safe-net solvers: no abstol (KrySP*.c)
+        for m in SAFE_FORMATS[fmt]:
+            rs = [C.c_short] if m.endswith("gmres") else []
+            getattr(L, f"fasp_solver_d{fmt}_{m}").argtypes = [P(mat), V_, V_, P(T.precond), C.c_double, C.c_int] + rs + [C.c_short, C.c_short]
+    L.fasp_solver_dcsr_itsolver_s.argtypes = [M_, V_, V_, P(T.precond), P(T.ITS_param)]
+    L.fasp_solver_dcsr_krylov_s.argtypes = [M_, V_, V_, P(T.ITS_param)]
+    L.fasp_hip_safe_update_selftest.argtypes = [C.c_int, C.c_int, C.c_int, D_]
+    L.fasp_hip_plugin_solve_seconds.argtypes = []
+    L.fasp_hip_plugin_solve_seconds.restype = C.c_double
     return L
 
 
@@ -966,3 +981,45 @@ def solver_amg(ia, ja, a, b, x, amgparam):
     assert x.dtype == np.float64 and x.flags.c_contiguous
     xv = T.dvector(len(x), T.dp(x))
     return lib().fasp_solver_amg(C.byref(A), C.byref(bv), C.byref(xv), C.byref(amgparam))
+
+
+
+def solver_safe(fmt, method, A, b, x, pc=None, tol=1e-8, maxit=500, restart=25, stop_type=T.STOP_REL_RES, print_level=0):
+    """fasp_solver_d<fmt>_<method> (KrySP*.c: the Krylov methods with a safety net): fmt "csr" / "bsr" / "str", method one of
+    SAFE_FORMATS[fmt], A the matching struct of _types (as_csr / as_bsr / as_str), pc a _types.precond or None.  x (numpy f64) is the
+    guess on entry and the solution on exit.  Returns the iteration count or a negative ERROR_* code."""
+    assert method in SAFE_FORMATS[fmt] and x.dtype == np.float64 and x.flags.c_contiguous
+    bv, _b = T.as_vec(b)
+    xv = T.dvector(len(x), T.dp(x))
+    args = [C.byref(A), C.byref(bv), C.byref(xv), C.byref(pc) if pc is not None else None, tol, maxit]
+    if method.endswith("gmres"):
+        args.append(restart)
+    return getattr(lib(), f"fasp_solver_d{fmt}_{method}")(*args, stop_type, print_level)
+
+
+def solver_dcsr_itsolver_s(ia, ja, a, b, x, itparam, pc=None):
+    """fasp_solver_dcsr_itsolver_s (SolCSR.c:163): the safe-net method itparam.itsolver_type selects, with the caller's precond."""
+    A, _keep = T.as_csr(ia, ja, a)
+    bv, _b = T.as_vec(b)
+    assert x.dtype == np.float64 and x.flags.c_contiguous
+    xv = T.dvector(len(x), T.dp(x))
+    return lib().fasp_solver_dcsr_itsolver_s(C.byref(A), C.byref(bv), C.byref(xv), C.byref(pc) if pc is not None else None, C.byref(itparam))
+
+
+def solver_dcsr_krylov_s(ia, ja, a, b, x, itparam):
+    """fasp_solver_dcsr_krylov_s (SolCSR.c:295): fasp_solver_dcsr_itsolver_s without a preconditioner."""
+    A, _keep = T.as_csr(ia, ja, a)
+    bv, _b = T.as_vec(b)
+    assert x.dtype == np.float64 and x.flags.c_contiguous
+    xv = T.dvector(len(x), T.dp(x))
+    return lib().fasp_solver_dcsr_krylov_s(C.byref(A), C.byref(bv), C.byref(xv), C.byref(itparam))
+
+
+def safe_update_selftest(which, n, seed):
+    """fasp_hip_safe_update_selftest -> (elementwise mismatches, scalars of the fused kernel, scalars of the BLAS-1 sequence)."""
+    out = np.zeros(18)
+    st = lib().fasp_hip_safe_update_selftest(which, n, seed, T.dp(out))
+    if st < 0:
+        raise RuntimeError(f"fasp_hip_safe_update_selftest failed with status {st}")
+    nq = int(out[1])
+    return int(out[0]), out[2:2 + nq].copy(), out[10:10 + nq].copy()

@@ -7,6 +7,7 @@ static KOps csr_ops(fasp_hip_amg* h, int level, bool with_pc);
 // forward declarations (the coarse fallback and the preconditioner call each other's owners)
 static int precond_amg(fasp_hip_amg* h, double* r, double** z);
 static void itinfo(int ptrlvl, int stop_type, int iter, double relres, double absres, double factor);
+static int safe_x_update(bool fused, int n, const double* r, const double* x_in, double* x_out, double* red);   // safe_krylov.hip.h
 struct PcgOut { double relres, absres, normr0; };
 struct Hist {
     double* h; int cap; int n;
@@ -52,6 +53,9 @@ static void d_scale(int n, double a, double* x)
 //   mode 0  fasp_solver_dcsr_pvgmres    KryPvgmres.c:66-412
 //   mode 1  fasp_solver_dcsr_pvfgmres   KryPvfgmres.c:67-384   (flexible)
 //   mode 2  fasp_solver_dcsr_spvgmres   KrySPvgmres.c:68-441   (safe net; coarse-level fallback)
+//   mode 4  fasp_solver_dcsr_spgmres    KrySPgmres.c:66-386    (safe net, fixed restart: the text of mode 2 without the restart adaptation)
+//   + 8 (modes 2 and 4, the public safe entries): the cycle-end x += .. carries isnan and the norms (k_safe_x_update) and x / x_best
+//       are two buffers whose roles swap -- the caller's x is written once, at exit (safe_krylov.hip.h); without it mode 2 keeps its launches
 // The scalar control flow (restart adaptation, Givens rotations, back substitution, false-
 // convergence check, best-iterate safety net) runs on the host exactly as in the reference;
 // the modified Gram-Schmidt chain runs on the device without host round trips (k_mgs_step).
@@ -61,8 +65,10 @@ static void d_scale(int n, double a, double* x)
 static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double tol, double abstol, int MaxIt,
                         int restart, int StopType, int PrtLvl, Hist* hist, PcgOut* out)
 {
-    const bool fixed = mode_in == 3;       // mode 3: fixed restart, fasp_solver_d*_pgmres (KryPgmres.c:66) ...
-    const int  mode = fixed ? 0 : mode_in; // ... the text of mode 0 with four differences
+    const bool sfused = (mode_in & 8) != 0;
+    const bool fixed = (mode_in & 7) == 3;   // mode 3: fixed restart, fasp_solver_d*_pgmres (KryPgmres.c:66) ...
+    const bool sfix = (mode_in & 7) == 4;    // mode 4: mode 2 with the restart it was given
+    const int  mode = fixed ? 0 : sfix ? 2 : (mode_in & 7);   // ... the text of mode 0 with four differences
     const int n = K.n;
     const size_t nv = K.nvec;
     const bool dist = K.dist;
@@ -90,6 +96,8 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
     double** p = W.data();
     double*  w = W[Restart1];
     double*  x_best = W[Restart1 + 1];
+    double* const x_caller = x;            // sfused: x and x_best walk over these two buffers
+    double* const x_spare = x_best;
     double** z = mode == 1 ? W.data() + Restart1 + 2 : nullptr;
     double*  r = nullptr;  // preconditioned / work vector (may alias an internal buffer)
     std::vector<double> rs(Restart1 + 1, 0.0), c(Restart + 1, 0.0), sn(Restart + 1, 0.0);
@@ -109,7 +117,8 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
 
     if (PrtLvl > PRINT_NONE)
         std::printf(fixed ? "\nCalling GMRes solver (%s) ...\n" : mode == 0 ? "\nCalling VGMRes solver (%s) ...\n"
-                    : mode == 1 ? "\nCalling VFGMRes solver (%s) ...\n" : "\nCalling Safe VGMRes solver (%s) ...\n", K.fmt);
+                    : mode == 1 ? "\nCalling VFGMRes solver (%s) ...\n" : sfix ? "\nCalling Safe GMRes solver (%s) ...\n"
+                    : "\nCalling Safe VGMRes solver (%s) ...\n", K.fmt);
 
     if ((st = true_residual(x, p[0])) < 0) return st;
     if (mode == 1) { if (d_dot(n, b, b, red, dist) < 0) return ERROR_MISC; b_norm = std::sqrt(red[0]); }
@@ -163,7 +172,7 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
         if (mode == 1 && r_norm == 0.0) { if (out) { out->relres = 0.0; out->absres = 0.0; out->normr0 = den_norm; } return iter; }
         if (mode != 1) d_scale(n, 1.0 / r_norm, p[0]);
 
-        if (!fixed) {
+        if (!fixed && !sfix) {
             if (cr > cr_max || iter == 0) Restart = restart_max;
             else if (cr < cr_min) { /* keep */ }
             else { if (Restart - d > restart_min) Restart -= d; else Restart = restart_max; }
@@ -258,9 +267,19 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
             for (j = i - 2; j >= 0; j--) d_axpy(n, rs[j], p[j], w);
             if ((st = apply_pc(w, &r)) < 0) return st;
         }
-        d_axpy(n, 1.0, r, x);
+        if (sfused) {  // the same safety net with the passes folded into the update and no copy of the iterate
+            double* const xo = (x == x_best) ? (x == x_caller ? x_spare : x_caller) : x;
+            if (safe_x_update(true, n, r, x, xo, red) < 0) return ERROR_MISC;
+            x = xo;
+            if (red[2] > 0.0) { absres = BIGREAL; goto RESTORE_BESTSOL; }
+            if (absres < absres_best - maxdiff) {
+                absres_best = absres;
+                iter_best = iter;
+                x_best = x;
+            }
+        } else d_axpy(n, 1.0, r, x);
 
-        if (mode == 2) {  // safety net, KrySPvgmres.c:287-299
+        if (mode == 2 && !sfused) {  // safety net, KrySPvgmres.c:287-299
             if (d_norms(n, x, red, dist) < 0) return ERROR_MISC;
             if (std::isnan(red[0])) { absres = BIGREAL; goto RESTORE_BESTSOL; }
             if (absres < absres_best - maxdiff) {
@@ -324,17 +343,24 @@ static int gmres_device(KOps& K, const double* b, double* x, int mode_in, double
 RESTORE_BESTSOL:
     if (mode == 2 && iter != iter_best) {  // KrySPvgmres.c:357-389
         if ((st = true_residual(x_best, w)) < 0) return st;
-        if (d_dot(n, w, w, red, dist) < 0) return ERROR_MISC;
+        if (StopType == STOP_REL_PRECRES) {  // :384-391
+            double* zz = nullptr;
+            if ((st = apply_pc(w, &zz)) < 0) return st;
+            if (d_dot(n, zz, w, red, dist) < 0) return ERROR_MISC;
+            red[0] = std::fabs(red[0]);
+        } else if (d_dot(n, w, w, red, dist) < 0) return ERROR_MISC;
         absres_best = std::sqrt(red[0]);
         if (absres > absres_best + maxdiff || std::isnan(absres)) {
             if (PrtLvl > PRINT_NONE)
                 std::printf("### WARNING: Discard current iteration. Restore iteration %d!\n", iter_best);
-            HIPCK(hipMemcpyAsync(x, x_best, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+            if (sfused) x = x_best;
+            else HIPCK(hipMemcpyAsync(x, x_best, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
             relres = absres_best / absres0;
         }
     }
 
 FINISHED:
+    if (x != x_caller) HIPCK(hipMemcpyAsync(x_caller, x, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     {
         const double fr = (mode == 1) ? r_norm / den_norm : relres;
         if (PrtLvl > PRINT_NONE) {

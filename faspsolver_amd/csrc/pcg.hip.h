@@ -288,12 +288,18 @@ static int cg_smooth(fasp_hip_amg* h, int level, int nsweeps)
 // SolBSR.c:55-150) and the plug-in level (solver.hip, krylov_plugin).
 // ---------------------------------------------------------------------------
 enum KMethod { K_CG = SOLVER_CG, K_BiCGstab = SOLVER_BiCGstab, K_MinRes = SOLVER_MinRes, K_GMRES = SOLVER_GMRES,
-               K_VGMRES = SOLVER_VGMRES, K_VFGMRES = SOLVER_VFGMRES, K_GCG = SOLVER_GCG, K_GCR = SOLVER_GCR };
-constexpr unsigned kbit(int m) { return (m >= K_CG && m <= K_GCR) ? 1u << m : 0u; }
+               K_VGMRES = SOLVER_VGMRES, K_VFGMRES = SOLVER_VFGMRES, K_GCG = SOLVER_GCG, K_GCR = SOLVER_GCR,
+               // the safe-net methods (KrySP*.c): no itsolver_type of the non-safe dispatchers reaches them (SolCSR.c:163 maps CG, BiCGstab, ... onto them)
+               K_SPCG = 16, K_SPBiCGstab = 17, K_SPMinRes = 18, K_SPGMRES = 19, K_SPVGMRES = 20 };
+constexpr unsigned kbit(int m) { return ((m >= K_CG && m <= K_GCR) || (m >= K_SPCG && m <= K_SPVGMRES)) ? 1u << m : 0u; }
 // the methods a family of entry points offers
 constexpr unsigned K_OFFER_BSR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_VFGMRES);
 constexpr unsigned K_OFFER_MATFREE = K_OFFER_BSR | kbit(K_MinRes) | kbit(K_GCG);
 constexpr unsigned K_OFFER_ALL = K_OFFER_MATFREE | kbit(K_GCR);
+// ... and the safe-net methods the reference has for the format (KrySP*.c: BSR has no safe CG and no safe MinRes)
+constexpr unsigned K_OFFER_SAFE_BSR = kbit(K_SPBiCGstab) | kbit(K_SPGMRES) | kbit(K_SPVGMRES);
+constexpr unsigned K_OFFER_SAFE_CSR = K_OFFER_SAFE_BSR | kbit(K_SPCG) | kbit(K_SPMinRes);
+constexpr unsigned K_OFFER_SAFE_STR = K_OFFER_SAFE_CSR;
 struct KParams { double tol, abstol; int MaxIt, restart, StopType, PrtLvl; };
 
 // mf_texts: the reference's older texts for mxv_matfree (CG, MinRes and the GMRES variants; they keep no residual history);
@@ -308,6 +314,12 @@ static int krylov_run(KOps& K, KMethod method, unsigned offered, bool mf_texts, 
     if (mf_texts && gm)
         return gmres_mf_device(K, method != K_GMRES, method == K_VFGMRES, b, u, P.tol, P.MaxIt, P.restart, P.StopType, P.PrtLvl, out);
     switch (method) {
+        case K_SPCG: return spcg_device(K, b, u, P.tol, P.MaxIt, P.StopType, P.PrtLvl, out);
+        case K_SPBiCGstab: return spbcgs_device(K, b, u, P.tol, P.MaxIt, P.StopType, P.PrtLvl, out);
+        case K_SPMinRes: return spminres_device(K, b, u, P.tol, P.MaxIt, P.StopType, P.PrtLvl, out);
+        case K_SPGMRES: case K_SPVGMRES:   // safe net: fixed restart (mode 4), variable restart (mode 2); + 8: the fused cycle end
+            return gmres_device(K, b, u, (method == K_SPGMRES ? 4 : 2) | (g_tune.safe_fused ? 8 : 0), P.tol, P.abstol, P.MaxIt, P.restart,
+                                P.StopType, P.PrtLvl, hist, out);
         case K_CG: return pcg_device(K, PcgVecs{b, u, p, t, r}, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, *hist, *out);
         case K_BiCGstab: return bicgstab_device(K, b, u, P.tol, P.MaxIt, P.PrtLvl, hist, out);
         case K_MinRes: return minres_device(K, b, u, P.tol, P.abstol, P.MaxIt, P.StopType, P.PrtLvl, hist, out);

@@ -163,6 +163,8 @@ static inline int vec_grid(int n)
 
 #include "krylov.hip.h"
 
+#include "safe_krylov.hip.h"
+
 #include "cycles.hip.h"
 
 #include "pcg.hip.h"
@@ -1389,9 +1391,9 @@ IluDev* ilu_lookup_none(precond*, int, std::unique_ptr<IluDev, void (*)(IluDev*)
 constexpr unsigned K_OFFER_STR = kbit(K_CG) | kbit(K_BiCGstab) | kbit(K_GMRES) | kbit(K_VGMRES) | kbit(K_MinRes);
 
 //                              fmt        ctx_first bad_bsr_dies refuse_multi_rank refuse_empty find_amg          borrow_resident fused_mxv_dot bind_diag      ilu_lookup          handle_ilu_checked mf_texts offered
-const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_pc_csr,   ilu_of_precond,     false,             false,   K_OFFER_ALL};
-const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR};
-const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_pc_str,   ilu_lookup_none,    false,             false,   K_OFFER_STR};
+const KFamily FAMILY_CSR     = {"CSR",     true,     false,       true,             false,       find_amg_csr,     true,           true,         bind_pc_csr,   ilu_of_precond,     false,             false,   K_OFFER_ALL | K_OFFER_SAFE_CSR};
+const KFamily FAMILY_BSR     = {"BSR",     false,    true,        false,            false,       find_amg_bsr,     false,          false,        bind_diag_bsr, ilu_of_precond_bsr, true,              false,   K_OFFER_BSR | K_OFFER_SAFE_BSR};
+const KFamily FAMILY_STR     = {"STR",     true,     false,       true,             false,       find_amg_none,    false,          false,        bind_pc_str,   ilu_lookup_none,    false,             false,   K_OFFER_STR | K_OFFER_SAFE_STR};
 const KFamily FAMILY_MATFREE = {"MatFree", true,     false,       true,             true,        find_amg_matfree, false,          false,        nullptr,       ilu_of_precond,     false,             true,    K_OFFER_MATFREE};
 
 // K.pc for the caller's `precond`: a device AMG handle (S.h / S.hb, found by F.find_amg), a device ILU, a device (block-)
@@ -1445,6 +1447,7 @@ struct KOperator {
     }
 };
 
+double g_plugin_run_seconds = 0.0;   // fasp_hip_plugin_solve_seconds
 int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op, dvector* b, dvector* u, precond* pc,
                   const KParams& P)
 {
@@ -1530,7 +1533,9 @@ int krylov_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op
     if ((st = bind_precond(F, pc, n, Ab ? Ab->nb : As ? As->nc : 1, S, K)) < 0) return st;
     Hist   H{nullptr, 0, 0};
     PcgOut po{BIGREAL, BIGREAL, BIGREAL};
-    st = krylov_run(K, method, F.offered, F.mf_texts, P, db.d, du.d, sp, stv, sr, &H, &po);
+    const double t_run = wall_seconds();
+    st = krylov_run(K, method, F.offered, F.mf_texts, P, db.d, du.d, sp, stv, sr, &H, &po);   // (every driver ends with a stream synchronise)
+    g_plugin_run_seconds = wall_seconds() - t_run;
     du.get(u->val);
     // a single-launch ILU solve (of the preconditioner, or of a block handle's cycle) that timed out
     if ((S.ilu || (S.strilu && S.strilu->used_pipe) || (F.handle_ilu_checked && S.hb && S.hb->L[0].ilu)) && st >= 0 && seq_err_check() < 0) st = ERROR_MISC;
@@ -1798,6 +1803,145 @@ int fasp_solver_dbsr_krylov_diag(dBSRmat* A, dvector* b, dvector* x, ITS_param* 
 
 #include "str_api.hip.h"
 #include "csr_swz_api.hip.h"
+
+// ---------------------------------------------------------------------------
+// The Krylov methods with a safety net (KrySPcg.c, KrySPbcgs.c, KrySPminres.c, KrySPgmres.c, KrySPvgmres.c) and their dispatchers
+// (SolCSR.c:163 / :295): the plug-in driver with the drivers of safe_krylov.hip.h.  The reference's prototypes have no abstol.
+// Without a usable device these entries print why and return ERROR_MISC with x untouched; several ranks are refused (one GPU).
+// ---------------------------------------------------------------------------
+namespace {
+int safe_plugin(const char* fn, const KFamily& F, KMethod method, KOperator op, const dvector* b, dvector* u, precond* pc,
+                const KParams& P)
+{
+    if (ctx_init() < 0) {
+        std::printf("### ERROR: %s: no usable HIP device and no CPU fallback in libfasp_hip\n", fn);
+        return ERROR_MISC;
+    }
+    if (comm_size() > 1) {
+        std::printf("### ERROR: %s: the safe-net solvers run on one GPU, this job has %d ranks\n", fn, comm_size());
+        return ERROR_INPUT_PAR;
+    }
+    return krylov_plugin(fn, F, method, op, const_cast<dvector*>(b), u, pc, P);
+}
+}  // namespace
+// KrySPcg.c:60
+int fasp_solver_dcsr_spcg(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                          const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_CSR, K_SPCG, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+// KrySPbcgs.c:61
+int fasp_solver_dcsr_spbcgs(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_CSR, K_SPBiCGstab, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+// KrySPminres.c:60
+int fasp_solver_dcsr_spminres(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                              const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_CSR, K_SPMinRes, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+// KrySPgmres.c:66
+int fasp_solver_dcsr_spgmres(const dCSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_CSR, K_SPGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+// KrySPvgmres.c:68
+int fasp_solver_dcsr_spvgmres(const dCSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_CSR, K_SPVGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+// KrySPbcgs.c:452, KrySPgmres.c:409, KrySPvgmres.c:449
+int fasp_solver_dbsr_spbcgs(const dBSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_BSR, K_SPBiCGstab, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+int fasp_solver_dbsr_spgmres(const dBSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_BSR, K_SPGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+int fasp_solver_dbsr_spvgmres(const dBSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_BSR, K_SPVGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+// KrySPcg.c:726, KrySPbcgs.c:1234, KrySPminres.c:962, KrySPgmres.c:1095, KrySPvgmres.c:1210
+int fasp_solver_dstr_spcg(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                          const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_STR, K_SPCG, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+int fasp_solver_dstr_spbcgs(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_STR, K_SPBiCGstab, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+int fasp_solver_dstr_spminres(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                              const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_STR, K_SPMinRes, A, b, u, pc, {tol, 0.0, MaxIt, 0, StopType, PrtLvl});
+}
+int fasp_solver_dstr_spgmres(const dSTRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_STR, K_SPGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+int fasp_solver_dstr_spvgmres(const dSTRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl)
+{
+    FASP_ENTRY();
+    return safe_plugin(__func__, FAMILY_STR, K_SPVGMRES, A, b, x, pc, {tol, 0.0, MaxIt, restart, StopType, PrtLvl});
+}
+// SolCSR.c:163: an itsolver_type without a safe text is refused before any work, as there
+int fasp_solver_dcsr_itsolver_s(dCSRmat* A, dvector* b, dvector* x, precond* pc, ITS_param* itparam)
+{
+    FASP_ENTRY();
+    if (!itparam) return ERROR_INPUT_PAR;
+    const short prtlvl = itparam->print_level, stop_type = itparam->stop_type, restart = (short)itparam->restart;
+    const int MaxIt = itparam->maxit;
+    const double tol = itparam->tol, t0 = wall_seconds();
+    int iter;
+    its_check(tol, MaxIt);
+    switch (itparam->itsolver_type) {
+        case SOLVER_CG: iter = fasp_solver_dcsr_spcg(A, b, x, pc, tol, MaxIt, stop_type, prtlvl); break;
+        case SOLVER_BiCGstab: iter = fasp_solver_dcsr_spbcgs(A, b, x, pc, tol, MaxIt, stop_type, prtlvl); break;
+        case SOLVER_MinRes: iter = fasp_solver_dcsr_spminres(A, b, x, pc, tol, MaxIt, stop_type, prtlvl); break;
+        case SOLVER_GMRES: iter = fasp_solver_dcsr_spgmres(A, b, x, pc, tol, MaxIt, restart, stop_type, prtlvl); break;
+        case SOLVER_VGMRES: iter = fasp_solver_dcsr_spvgmres(A, b, x, pc, tol, MaxIt, restart, stop_type, prtlvl); break;
+        default:
+            std::printf("### ERROR: Unknown iterative solver type %d! [%s]\n", itparam->itsolver_type, __func__);
+            return ERROR_SOLVER_TYPE;
+    }
+    print_itsolver_time(prtlvl, iter, wall_seconds() - t0);
+    return iter;
+}
+// SolCSR.c:295
+int fasp_solver_dcsr_krylov_s(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam)
+{
+    FASP_ENTRY();
+    if (!itparam) return ERROR_INPUT_PAR;
+    const double t0 = wall_seconds();
+    const int status = fasp_solver_dcsr_itsolver_s(A, b, x, nullptr, itparam);
+    if (itparam->print_level >= PRINT_MIN) std::printf("Krylov method totally costs %.4f seconds.\n", wall_seconds() - t0);
+    return status;
+}
 
 // ---------------------------------------------------------------------------
 // Matrix-free interface of the reference (fasp.h:1109 mxv_matfree, SolMatFree.c): Krylov methods
@@ -2293,6 +2437,7 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "seq_chain_touch")) g_tune.seq_chain_touch = value;   // chain form: blocks by which a workgroup of its own on the chain's XCD touches the band planes ahead (8; 0: the importer wave does, four ahead)
     else if (!std::strcmp(key, "seq_chain_touch_t1")) g_tune.seq_chain_touch_t1 = value;   // ... and tier 1's entries of those blocks (1, default)
     else if (!std::strcmp(key, "seq_zero_skip")) g_tune.seq_zero_skip = value;   // sequential sweeps: the parallel pass of a sweep that starts from the zero vector reads b only (1, default) or every entry (0)
+    else if (!std::strcmp(key, "safe_fused")) g_tune.safe_fused = value;       // safe-net Krylov solvers: the fused update kernels and the swapping iterate buffers (1, default) or the reference's pass-by-pass sequence over the existing BLAS-1 launches with a real copy to u_best (0: A/B, second implementation) -- same elementwise bits
     else if (!std::strcmp(key, "pcg_fold")) g_tune.pcg_fold = value;           // one rank: (t,p) and (z,r) are summed from their partials by the kernels that divide by them (1, default) or by a k_finalize launch each (0)
     else if (!std::strcmp(key, "spcg_spec")) g_tune.spcg_spec = value;         // persistent coarse CG: the true residual of Check III queued behind the kernel, one host wait per coarse solve (1, default) or two (0)
     else if (!std::strcmp(key, "ev_every")) g_tune.ev_every = value;           // the level-0 t = A p launch inside a solve is bracketed by an event pair every n-th iteration (4; 1: every one)
@@ -2306,6 +2451,83 @@ int fasp_hip_tune(const char* key, int value)
     else if (!std::strcmp(key, "wrows")) g_tune.wrows = value;
     else if (!std::strcmp(key, "wcap")) g_tune.wcap = value;
     else return ERROR_INPUT_PAR;
+    return FASP_SUCCESS;
+}
+
+// measurement entry: wall seconds the last plug-in Krylov solve of this process spent in its driver (operator upload, preconditioner
+// binding and the copy of x back to the host excluded)
+double fasp_hip_plugin_solve_seconds(void)
+{
+    FASP_ENTRY();
+    return g_plugin_run_seconds;
+}
+
+// test entry: update step `which` of the safe-net solvers (safe_krylov.hip.h) in its fused form and as the reference's sequence over the
+// existing BLAS-1 launches, on the same inputs (fasp_hip_dev.h has the inputs and the layout of out)
+int fasp_hip_safe_update_selftest(int which, int n, int seed, double* out)
+{
+    FASP_ENTRY();
+    if (!out || n < 1 || which < 0 || which > 5 || seed < 0) return ERROR_INPUT_PAR;
+    if (ctx_init() < 0) return ERROR_MISC;
+    constexpr int NV = 7;   // vectors 0 .. 6: the inputs, by the step's own list
+    const double alpha = 0.37, omega = -0.61, beta = 1.29;
+    const bool nans = seed >= 1000;
+    auto value = [seed](int k, int i) {   // splitmix64 of (i, seed, k) -> [-1, 1)
+        unsigned long long z = ((unsigned long long)i + 1ull) * 0x9E3779B97F4A7C15ull + (unsigned long long)seed * 0xBF58476D1CE4E5B9ull +
+                               (unsigned long long)k * 0x94D049BB133111EBull;
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
+    };
+    std::vector<double> h((size_t)n), g0((size_t)n), g1((size_t)n);
+    TmpVec* v[2][NV + 1] = {};   // two sets (fused, sequence); vector NV: the second iterate buffer
+    std::vector<std::unique_ptr<TmpVec>> own;
+    for (int set = 0; set < 2; ++set)
+        for (int k = 0; k <= NV; ++k) {
+            for (int i = 0; i < n; ++i) h[(size_t)i] = k == NV ? 0.0 : value(k, i);
+            if (k == 0 && nans) h[0] = h[(size_t)(n / 2)] = h[(size_t)n - 1] = std::nan("");   // vector 0 is the iterate
+            own.emplace_back(new TmpVec(h.data(), (size_t)n));
+            if (!own.back()->d) return ERROR_ALLOC_MEM;
+            v[set][k] = own.back().get();
+        }
+    double red[2][8] = {};
+    int nq = 0, nout = 0, outs[4] = {0, 0, 0, 0};   // the step's output vectors
+    int st = 0;
+    for (int set = 0; set < 2 && st >= 0; ++set) {
+        const bool fused = set == 0;
+        auto D = [&](int k) { return v[set][k]->d; };
+        // the fused form writes the iterate OUT OF PLACE here (vector NV), the sequence in place (vector 0): both are compared
+        SafeIterate U(D(0), D(NV), n, fused);
+        if (fused) U.best = U.cur;
+        switch (which) {
+            case 0:   // u = 0, p = 1, t = 2, r = 3
+                st = safe_cg_update(fused, n, alpha, D(1), D(2), U, D(3), red[set]); nq = 5; nout = 2; outs[0] = 0; outs[1] = 3; break;
+            case 1:   // r = 1, z = 2 -> s = 3
+                safe_bcgs_s(fused, n, alpha, D(1), D(2), D(3)); nq = 0; nout = 1; outs[0] = 3; break;
+            case 2:   // u = 0, pp = 1, sp = 2, s = 3, t = 4, rho = 5 -> r = 6
+                st = safe_bcgs_update(fused, n, alpha, omega, D(1), D(2), D(2), U, D(3), D(4), D(6), D(5), red[set]);
+                nq = 6; nout = 4; outs[0] = 0; outs[1] = 2; outs[2] = 3; outs[3] = 6; break;
+            case 3:   // r = 1, z = 2, p = 3
+                safe_bcgs_p(fused, n, omega, beta, D(1), D(2), D(3)); nq = 0; nout = 1; outs[0] = 3; break;
+            case 4:   // t = 1, s = 2
+                st = safe_dot2(fused, n, D(1), D(2), red[set]); nq = 2; nout = 0; break;
+            default: {   // x = 0, r = 1
+                double* const xo = fused ? D(NV) : D(0);
+                st = safe_x_update(fused, n, D(1), D(0), xo, red[set]); U.cur = xo; nq = 3; nout = 1; outs[0] = 0; break;
+            }
+        }
+        if (fused && U.cur != D(0)) std::swap(v[set][0], v[set][NV]);   // vector 0 of the set: where the iterate is now
+    }
+    if (st < 0) return st;
+    HIPCK(hipStreamSynchronize(g_ctx.stream));
+    long long mismatches = 0;
+    for (int o = 0; o < nout; ++o) {
+        v[0][outs[o]]->get(g0.data());
+        v[1][outs[o]]->get(g1.data());
+        for (int i = 0; i < n; ++i) mismatches += std::memcmp(&g0[(size_t)i], &g1[(size_t)i], sizeof(double)) != 0;
+    }
+    out[0] = (double)mismatches;
+    out[1] = (double)nq;
+    for (int k = 0; k < 8; ++k) { out[2 + k] = red[0][k]; out[10 + k] = red[1][k]; }
     return FASP_SUCCESS;
 }
 

@@ -23,6 +23,9 @@
  *   fasp_blas_darray_{dotprod,norm2,norminf,axpy,axpby}
  *                                                   base/src/BlaArray.c:771/691/719/90/620
  *   fasp_smoother_dcsr_jacobi                       base/src/ItrSmootherCSR.c:98
+ *   fasp_solver_d{csr,bsr,str}_sp{cg,bcgs,minres,gmres,vgmres}
+ *                                                   base/src/KrySPcg.c, KrySPbcgs.c, KrySPminres.c, KrySPgmres.c, KrySPvgmres.c
+ *   fasp_solver_dcsr_itsolver_s / _krylov_s         base/src/SolCSR.c:163 / :295
  *
  * The `fasp_hip_*` functions are extensions (no reference counterpart): they
  * expose the device-resident objects behind fasp_solver_dcsr_krylov_amg so a
@@ -790,6 +793,43 @@ int fasp_solver_dcsr_pvgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, co
 int fasp_solver_dcsr_pvfgmres(dCSRmat* A, dvector* b, dvector* x, precond* pc, const double tol,
                               const double abstol, const int MaxIt, const short restart,
                               const short StopType, const short PrtLvl);
+/* ---- the Krylov methods with a safety net (KrySP*.c) and their dispatchers (SolCSR.c:163 / :295) ----
+ * The best iterate seen so far is kept and handed back when the iteration breaks down, produces a NaN, or ends (also at MaxIt) on an
+ * iterate that is worse by more than tol * STAG_RATIO; "### WARNING: Discard current iteration. Restore iteration %d!" says so.  The
+ * reference's prototypes (no abstol), return codes and printed lines.  All three stop types.  `pc`: as for the non-safe entries of the
+ * format -- a device AMG handle, fasp_precond_ilu, the (block-)diagonal and Schwarz preconditioners and the structured ILU / block
+ * Gauss-Seidel ones stay in HBM, any other pc->fct is called on the host.  One GPU (several ranks: message, ERROR_INPUT_PAR).  Without
+ * a usable device these entries print why and return ERROR_MISC with x untouched (no CPU fallback).  fasp_solver_dcsr_itsolver_s takes
+ * SOLVER_CG, _BiCGstab, _MinRes, _GMRES and _VGMRES; any other itsolver_type: "Unknown iterative solver type", ERROR_SOLVER_TYPE, before
+ * any work.  fasp_solver_dcsr_krylov_s: the same with pc = NULL and the timing line. */
+int fasp_solver_dcsr_spcg(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                          const short StopType, const short PrtLvl);                      /* KrySPcg.c:60 */
+int fasp_solver_dcsr_spbcgs(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl);                    /* KrySPbcgs.c:61 */
+int fasp_solver_dcsr_spminres(const dCSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                              const short StopType, const short PrtLvl);                  /* KrySPminres.c:60 */
+int fasp_solver_dcsr_spgmres(const dCSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl);    /* KrySPgmres.c:66 */
+int fasp_solver_dcsr_spvgmres(const dCSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl);   /* KrySPvgmres.c:68 */
+int fasp_solver_dcsr_itsolver_s(dCSRmat* A, dvector* b, dvector* x, precond* pc, ITS_param* itparam);   /* SolCSR.c:163 */
+int fasp_solver_dcsr_krylov_s(dCSRmat* A, dvector* b, dvector* x, ITS_param* itparam);                  /* SolCSR.c:295 */
+int fasp_solver_dbsr_spbcgs(const dBSRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl);                    /* KrySPbcgs.c:452 */
+int fasp_solver_dbsr_spgmres(const dBSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl);    /* KrySPgmres.c:409 */
+int fasp_solver_dbsr_spvgmres(const dBSRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl);   /* KrySPvgmres.c:449 */
+int fasp_solver_dstr_spcg(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                          const short StopType, const short PrtLvl);                      /* KrySPcg.c:726 */
+int fasp_solver_dstr_spbcgs(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                            const short StopType, const short PrtLvl);                    /* KrySPbcgs.c:1234 */
+int fasp_solver_dstr_spminres(const dSTRmat* A, const dvector* b, dvector* u, precond* pc, const double tol, const int MaxIt,
+                              const short StopType, const short PrtLvl);                  /* KrySPminres.c:962 */
+int fasp_solver_dstr_spgmres(const dSTRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                             short restart, const short StopType, const short PrtLvl);    /* KrySPgmres.c:1095 */
+int fasp_solver_dstr_spvgmres(const dSTRmat* A, const dvector* b, dvector* x, precond* pc, const double tol, const int MaxIt,
+                              short restart, const short StopType, const short PrtLvl);   /* KrySPvgmres.c:1210 */
 /* ---- the reference's own preconditioner objects (relink-only callers: tutorial/main/poisson-pcg.c:81,91) ----
  * fasp_precond_setup (PreCSR.c:46): PREC_AMG / PREC_FMG build the hierarchy on the host, upload it, and hand out
  * precond{data = precond_data*, fct = fasp_precond_amg | _amli | _namli | _famg}; mgl_data[l].A / P / R / cfmark show

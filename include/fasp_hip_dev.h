@@ -126,9 +126,34 @@ double fasp_hip_rap_time(const dCSRmat* R, const dCSRmat* A, const dCSRmat* P, i
  *     read at upload);
  *   Galerkin product on the device: rap_form (-1 (default) by the mean work per coarse row, 0 one lane per row, 1 one wavefront
  *     per row), rap_arena_kb (KiB of the table arena the rows are batched into) -- same bytes; device_rap (1: the AMG setups form
- *     their Galerkin products on the device whenever one is usable and there is one rank; 0 (default): on the host) -- same bytes.
+ *     their Galerkin products on the device whenever one is usable and there is one rank; 0 (default): on the host) -- same bytes;
+ *   safe-net Krylov solvers: safe_fused (1 (default): the fused update kernels of csrc/safe_krylov.hip.h and two iterate buffers whose
+ *     roles swap; 0: the reference's pass-by-pass sequence over the existing BLAS-1 launches with a real copy to u_best) -- the same
+ *     elementwise bits, sums in another order.
  * Unknown keys return ERROR_INPUT_PAR. */
 int fasp_hip_tune(const char* key, int value);
+/* test entry: update step `which` of the safe-net Krylov solvers (csrc/safe_krylov.hip.h) on vectors of length n >= 1, once as its fused
+ * kernel and once as the reference's sequence over the existing device BLAS-1 kernels, on the same inputs.
+ * Inputs: vector k (k = 0 .. 6), entry i = (double)(z >> 11) * 2^-53 * 2 - 1 with z = splitmix64's finaliser of
+ * (i + 1) * 0x9E3779B97F4A7C15 + seed * 0xBF58476D1CE4E5B9 + k * 0x94D049BB133111EB (mod 2^64: z ^= z >> 30, z *= 0xBF58476D1CE4E5B9,
+ * z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31); seed >= 1000: vector 0, the iterate, holds NaN in entries 0, n / 2 and n - 1.
+ * alpha = 0.37, omega = -0.61, beta = 1.29.
+ *   which  step (vectors by number)                                                                  scalars
+ *   0      safe CG / MinRes update: u(0) += alpha p(1), r(3) -= alpha t(2)                           r.r, u.u, p.p, max|u|, #NaN(u)
+ *   1      s(3) = r(1) - alpha z(2)                                                                  --
+ *   2      safe BiCGstab update: sp(2) = alpha pp(1) + omega sp, u(0) += sp, s(3) -= omega t(4),
+ *          r(6) = s, with rho(5)                                                                     (r,rho), sp.sp, u.u, r.r, max|u|, #NaN(u)
+ *   3      p(3) = r(1) + beta (p - omega z(2))                                                       --
+ *   4      two dots of t(1) with s(2)                                                                t.t, s.t
+ *   5      cycle end of the safe GMRES pair: x(0) += r(1)                                            x.x, max|x|, #NaN(x)
+ * out (18 doubles): [0] entries of the step's output vectors whose bit patterns differ between the two forms, [1] number of scalars,
+ * [2 ..] the fused form's scalars, [10 ..] the sequence's.  Maxima skip NaN entries (fmax).  The fused forms of 0, 2 and 5 write the
+ * iterate out of place.  < 0: error (no device: ERROR_MISC). */
+int fasp_hip_safe_update_selftest(int which, int n, int seed, double* out);
+/* measurement entry (tools/perf_safe_krylov.py): wall seconds the last Krylov solve of this process with a caller's `precond` (the
+ * fasp_solver_d{csr,bsr,str}_p* / _sp* entries and the matrix-free ones) spent in its iteration, from the first residual to the
+ * synchronise behind the last one; the upload of the operator, the binding of the preconditioner and the copy of x are outside. */
+double fasp_hip_plugin_solve_seconds(void);
 /* Which kernel served the last coarsest-level solve of a hierarchy, and how it ended (read-only; tests).  info (8 ints) =
  *   [0] family: 0 none yet, 1 k_spcg_dpp, 2 k_spcg_reg, 3 k_spcg_wave, 4 k_spcg_small, 5 k_spcg_fused, 6 k_spcg_persist,
  *       7 launch_csr<OP_MXV_DOT> + k_spcg_step_reg / k_spcg_step (the last family launched: a persistent kernel that gave
