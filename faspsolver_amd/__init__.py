@@ -86,6 +86,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_solver_dcsr_itsolver_s", "fasp_solver_dcsr_krylov_s", "fasp_solver_dbsr_spbcgs", "fasp_solver_dbsr_spgmres",
     "fasp_solver_dbsr_spvgmres", "fasp_solver_dstr_spcg", "fasp_solver_dstr_spbcgs", "fasp_solver_dstr_spminres",
     "fasp_solver_dstr_spgmres", "fasp_solver_dstr_spvgmres", "fasp_hip_safe_update_selftest", "fasp_hip_plugin_solve_seconds",
+    "fasp_hip_blas1_op",
 ]
 SAFE_METHODS = ("spcg", "spbcgs", "spminres", "spgmres", "spvgmres")   # the safe-net Krylov methods (KrySP*.c) ...
 SAFE_FORMATS = {"csr": SAFE_METHODS, "bsr": ("spbcgs", "spgmres", "spvgmres"), "str": SAFE_METHODS}   # ... the reference has per format
@@ -425,6 +426,7 @@ def lib():
     L.fasp_hip_safe_update_selftest.argtypes = [C.c_int, C.c_int, C.c_int, D_]
     L.fasp_hip_plugin_solve_seconds.argtypes = []
     L.fasp_hip_plugin_solve_seconds.restype = C.c_double
+    L.fasp_hip_blas1_op.argtypes = [C.c_int, C.c_int, C.c_int, I_, D_, P(D_), P(D_), D_, C.c_int, I_, D_, D_, I_, D_]
     return L
 
 
@@ -1023,3 +1025,30 @@ def safe_update_selftest(which, n, seed):
         raise RuntimeError(f"fasp_hip_safe_update_selftest failed with status {st}")
     nq = int(out[1])
     return int(out[0]), out[2:2 + nq].copy(), out[10:10 + nq].copy()
+
+
+BLAS1_KERNELS = ("cg_update", "axpby_beta", "mgs_step", "finalize", "dot", "norms", "norm1_nan", "axpy", "axpby", "axpyz", "axpy_self",
+                 "scale", "set", "poly_scale", "poly_start", "poly_step", "jacobi_zero", "l1_zero", "diag_precond", "bsr_dinv_apply", "pack")
+
+
+def blas1_op(kernel, n, vectors=(), scal=(), ipar=(), variant=0, partials=None, idx=None):
+    """fasp_hip_blas1_op (include/fasp_hip_dev.h): one launch of BLAS1_KERNELS[kernel] (or a name of it) on the caller's vectors, by slot.
+    Returns (status, dict): "vec" the vectors as the kernel left them (copies; the inputs stay), "red" the finalised scalars, "partials"
+    the raw per-block partials (quantities x grid), "grid", "pub" the published scalar.  status < 0: the dict holds what was passed in."""
+    k = BLAS1_KERNELS.index(kernel) if isinstance(kernel, str) else int(kernel)
+    vin = [np.ascontiguousarray(v, dtype=np.float64) for v in vectors]
+    out = [v.copy() for v in vin]
+    PA = T.c_double_p * 6
+    pin = PA(*([T.dp(v) for v in vin] + [None] * (6 - len(vin))))
+    pout = PA(*([T.dp(v) for v in out] + [None] * (6 - len(out))))
+    sc = np.zeros(8); sc[:len(scal)] = scal
+    ipr = np.zeros(4, dtype=np.int32); ipr[:len(ipar)] = ipar
+    part = None if partials is None else np.ascontiguousarray(partials, dtype=np.float64).reshape(-1)
+    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+    red = np.zeros(8); pout_part = np.zeros(8 * 2048); grid = np.zeros(2, dtype=np.int32); pub = np.zeros(1)
+    st = lib().fasp_hip_blas1_op(k, variant, n, T.ip(ipr), T.dp(sc), pin, pout, None if part is None else T.dp(part),
+                                 0 if part is None else len(part), None if ix is None else T.ip(ix), T.dp(red), T.dp(pout_part),
+                                 T.ip(grid), T.dp(pub))
+    G, nq = int(grid[0]), int(grid[1])
+    return st, {"vec": out, "red": red[:nq].copy(), "partials": pout_part[:nq * G].reshape(nq, G).copy() if nq else np.zeros((0, G)),
+                "grid": G, "pub": float(pub[0])}

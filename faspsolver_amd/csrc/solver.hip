@@ -2531,6 +2531,148 @@ int fasp_hip_safe_update_selftest(int which, int n, int seed, double* out)
     return FASP_SUCCESS;
 }
 
+// test entry: ONE launch of a BLAS-1 kernel (kernels.hip.h; k_pack of hierarchy.hip.h) on the caller's inputs, with the grid rule and the
+// context buffers of its production call site, followed by k_finalize where the solvers follow it with one (fasp_hip_dev.h has the
+// kernels, the variants and the layout of every argument).  No reference and no input generator live here.
+int fasp_hip_blas1_op(int kernel, int variant, int n, const int* ipar, const double* scal, const double* const* vin, double* const* vout,
+                      const double* part_in, int npart, const int* idx, double* red, double* part_out, int* grid, double* pub)
+{
+    FASP_ENTRY();
+    enum { CG_UPDATE, AXPBY_BETA, MGS_STEP, FINALIZE, DOT, NORMS, NORM1_NAN, AXPY, AXPBY, AXPYZ, AXPY_SELF, SCALE, SET, POLY_SCALE,
+           POLY_START, POLY_STEP, JACOBI_ZERO, L1_ZERO, DIAG_PRECOND, BSR_DINV_APPLY, PACK, NKERNEL };
+    constexpr int NSLOT = 6;
+    static const int nvec[NKERNEL] = {6, 2, 3, 0, 2, 1, 1, 2, 2, 3, 1, 1, 1, 3, 4, 6, 3, 3, 3, 3, 2};
+    static const int maxvar[NKERNEL] = {31, 1, 3, 0, 0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (kernel < 0 || kernel >= NKERNEL || variant < 0 || variant > maxvar[kernel] || n < 1 || n > (1 << 30) || !ipar || !scal || !vin ||
+        !vout || !red || !part_out || !grid || !pub || npart < 0)
+        return ERROR_INPUT_PAR;
+    for (int k = 0; k < nvec[kernel]; ++k)
+        if (!vin[k]) return ERROR_INPUT_PAR;
+    const bool folded = (kernel == CG_UPDATE || kernel == AXPBY_BETA || kernel == MGS_STEP) && (variant & 1);
+    if (kernel == CG_UPDATE && (variant & 8) && (variant & 16)) return ERROR_INPUT_PAR;   // one diagonal source
+    if (folded ? (npart < 1 || npart > MAXGRID || !part_in) : (kernel != FINALIZE && npart != 0)) return ERROR_INPUT_PAR;
+    int nq = 0;
+    unsigned maxmask = 0u;
+    size_t len[NSLOT] = {(size_t)n, (size_t)n, (size_t)n, (size_t)n, (size_t)n, (size_t)n};
+    if (kernel == FINALIZE) {   // n = G partials of each of ipar[0] quantities
+        nq = ipar[0]; maxmask = (unsigned)ipar[1];
+        if (nq < 1 || nq > 8 || n > MAXGRID || npart != nq * n || !part_in) return ERROR_INPUT_PAR;
+    } else if (kernel == BSR_DINV_APPLY) {
+        const int nb = ipar[0];
+        if (nb < 1 || n % nb != 0 || (long long)n * nb > (1ll << 30)) return ERROR_INPUT_PAR;
+        len[0] = (size_t)n * nb;
+    } else if (kernel == PACK) {   // n = nsend, ipar[0] = length of v
+        const int nv = ipar[0];
+        if (nv < 1 || !idx) return ERROR_INPUT_PAR;
+        for (int i = 0; i < n; ++i)
+            if (idx[i] < 0 || idx[i] >= nv) return ERROR_INPUT_PAR;
+        len[0] = (size_t)nv;
+    }
+    if (ctx_init() < 0) return ERROR_MISC;
+    hipStream_t s = g_ctx.stream;
+    std::unique_ptr<TmpVec> v[NSLOT];
+    double* d[NSLOT] = {};
+    for (int k = 0; k < nvec[kernel]; ++k) {
+        v[k].reset(new TmpVec(vin[k], len[k]));
+        if (!(d[k] = v[k]->d)) return ERROR_ALLOC_MEM;
+    }
+    TmpVec hh(nullptr, 4);   // the Hessenberg column of a GMRES workspace (k_mgs_step)
+    int* d_idx = nullptr;
+    struct IdxGuard { int*& p; ~IdxGuard() { if (p) (void)hipFree(p); } } idx_guard{d_idx};
+    if (!hh.d) return ERROR_ALLOC_MEM;
+    if (kernel == PACK) {
+        HIPCK(hipMalloc(&d_idx, sizeof(int) * (size_t)n));
+        HIPCK(hipMemcpy(d_idx, idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    // every scalar slot starts as NaN (all bits set): a slot the kernel should have written, and did not, shows
+    HIPCK(hipMemset(g_ctx.d_red, 0xff, sizeof(double) * RED_SLOTS));
+    HIPCK(hipMemset(hh.d, 0xff, sizeof(double) * 4));
+    auto put = [&](double* dst, const double* src, size_t cnt) { return hipMemcpy(dst, src, sizeof(double) * cnt, hipMemcpyHostToDevice); };
+    if (npart > 0) HIPCK(put(g_ctx.d_partials, part_in, (size_t)npart));
+    constexpr int ZR_SLOT = 12;   // pcg.hip.h: (z, r) of this and of the previous iteration
+    const double* partials = g_ctx.d_partials;   // where the kernel left its partials
+    const double* pub_dev = nullptr;
+    double* red_dev = g_ctx.d_red;
+    int G = 0;
+    auto cd = [](double* p) { return (const double*)p; };
+    switch (kernel) {
+        case CG_UPDATE: {   // vectors p, t, u, r, zx, zdiag; scal temp1, (t,p), zomega, zdiag_value
+            const bool t1dev = variant & 2, full = variant & 4, zarr = variant & 8, zval = variant & 16;
+            G = vec_grid(n);
+            if (!folded) HIPCK(put(g_ctx.d_red + 8, scal + 1, 1));
+            if (t1dev) HIPCK(put(g_ctx.d_red + ZR_SLOT, scal + 0, 1));
+            double* const upd = folded ? g_ctx.d_partials2 : g_ctx.d_partials;
+            hipLaunchKernelGGL(k_cg_update, dim3(G), dim3(BLOCK), 0, s, n, t1dev ? std::nan("") : scal[0], cd(g_ctx.d_red + 8),
+                               folded ? cd(g_ctx.d_partials) : (const double*)nullptr, folded ? npart : 0, cd(d[0]), cd(d[1]), d[2], d[3], upd,
+                               full ? 1 : 0, folded ? g_ctx.d_red + 8 : (double*)nullptr, (zarr || zval) ? d[4] : (double*)nullptr,
+                               zarr ? cd(d[5]) : (const double*)nullptr, scal[2], t1dev ? cd(g_ctx.d_red + ZR_SLOT) : (const double*)nullptr,
+                               scal[3]);
+            nq = full ? 5 : 1; maxmask = full ? 0x8u : 0u; partials = upd; pub_dev = g_ctx.d_red + 8;
+        } break;
+        case AXPBY_BETA:   // vectors x, y; scal num, den
+            G = vec_grid(n / 2 + 1);
+            if (!folded) HIPCK(put(g_ctx.d_red + ZR_SLOT + 1, scal + 0, 1));
+            HIPCK(put(g_ctx.d_red + ZR_SLOT, scal + 1, 1));
+            hipLaunchKernelGGL(k_axpby_beta, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), cd(g_ctx.d_red + ZR_SLOT + 1), cd(g_ctx.d_red + ZR_SLOT),
+                               d[1], cd(g_ctx.d_partials), folded ? npart : 0, g_ctx.d_red + ZR_SLOT + 1);
+            pub_dev = g_ctx.d_red + ZR_SLOT + 1;
+            break;
+        case MGS_STEP: {   // vectors pj, pi, pnext; scal h
+            double* const pnext = (variant & 2) ? d[2] : nullptr;
+            G = vec_grid(n);
+            if (folded) {
+                double* const mine = g_ctx.d_partials2 + 4 * MAXGRID;
+                hipLaunchKernelGGL(k_mgs_step, dim3(G), dim3(BLOCK), 0, s, n, (const double*)nullptr, cd(d[0]), d[1], cd(pnext), mine,
+                                   cd(g_ctx.d_partials), npart, hh.d);
+                partials = mine;
+            } else {
+                HIPCK(put(hh.d, scal + 0, 1));
+                hipLaunchKernelGGL(k_mgs_step, dim3(G), dim3(BLOCK), 0, s, n, cd(hh.d), cd(d[0]), d[1], cd(pnext), g_ctx.d_partials);
+            }
+            nq = 1; red_dev = hh.d + 1; pub_dev = hh.d;
+        } break;
+        case FINALIZE: G = n; break;
+        case DOT: G = vec_grid(n); hipLaunchKernelGGL(k_dot, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), cd(d[1]), g_ctx.d_partials); nq = 1; break;
+        case NORMS: G = vec_grid(n); hipLaunchKernelGGL(k_norms, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), g_ctx.d_partials); nq = 2; maxmask = 0x2u; break;
+        case NORM1_NAN: G = vec_grid(n); hipLaunchKernelGGL(k_norm1_nan, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), g_ctx.d_partials); nq = 2; break;
+        case AXPY: G = vec_grid(n / 2 + 1); hipLaunchKernelGGL(k_axpy, dim3(G), dim3(BLOCK), 0, s, n, scal[0], cd(d[0]), d[1]); break;
+        case AXPBY: G = vec_grid(n / 2 + 1); hipLaunchKernelGGL(k_axpby, dim3(G), dim3(BLOCK), 0, s, n, scal[0], cd(d[0]), scal[1], d[1]); break;
+        case AXPYZ:   // vectors x, y, z; variant 1: z is x, 2: z is y
+            G = vec_grid(n);
+            hipLaunchKernelGGL(k_axpyz, dim3(G), dim3(BLOCK), 0, s, n, scal[0], cd(d[0]), cd(d[1]), d[variant == 1 ? 0 : variant == 2 ? 1 : 2]);
+            break;
+        case AXPY_SELF: G = vec_grid(n); hipLaunchKernelGGL(k_axpy_self, dim3(G), dim3(BLOCK), 0, s, n, scal[0], d[0]); break;
+        case SCALE: G = vec_grid(n); hipLaunchKernelGGL(k_scale, dim3(G), dim3(BLOCK), 0, s, n, scal[0], d[0]); break;
+        case SET: G = vec_grid(n); hipLaunchKernelGGL(k_set, dim3(G), dim3(BLOCK), 0, s, n, scal[0], d[0]); break;
+        case POLY_SCALE: G = vec_grid(n); hipLaunchKernelGGL(k_poly_scale, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), cd(d[1]), d[2]); break;
+        case POLY_START:   // vectors dinv, rbar, v0, v1; scal k1, k2, k3
+            G = vec_grid(n);
+            hipLaunchKernelGGL(k_poly_start, dim3(G), dim3(BLOCK), 0, s, n, scal[0], scal[1], scal[2], cd(d[0]), cd(d[1]), d[2], d[3]);
+            break;
+        case POLY_STEP:   // vectors dinv, r, rbar, v0, v1, vnew; scal k4, k5
+            G = vec_grid(n);
+            hipLaunchKernelGGL(k_poly_step, dim3(G), dim3(BLOCK), 0, s, n, scal[0], scal[1], cd(d[0]), cd(d[1]), d[2], d[3], d[4], d[5]);
+            break;
+        case JACOBI_ZERO: G = vec_grid(n); hipLaunchKernelGGL(k_jacobi_zero, dim3(G), dim3(BLOCK), 0, s, n, scal[0], cd(d[0]), cd(d[1]), d[2]); break;
+        case L1_ZERO: G = vec_grid(n); hipLaunchKernelGGL(k_l1_zero, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), cd(d[1]), d[2]); break;
+        case DIAG_PRECOND: G = vec_grid(n); hipLaunchKernelGGL(k_diag_precond, dim3(G), dim3(BLOCK), 0, s, n, cd(d[0]), cd(d[1]), d[2]); break;
+        case BSR_DINV_APPLY: G = vec_grid(n); hipLaunchKernelGGL(k_bsr_dinv_apply, dim3(G), dim3(BLOCK), 0, s, n, ipar[0], cd(d[0]), cd(d[1]), d[2]); break;
+        default: G = vec_grid(n); hipLaunchKernelGGL(k_pack, dim3(G), dim3(BLOCK), 0, s, n, (const int*)d_idx, cd(d[0]), d[1]); break;
+    }
+    if (nq > 0) hipLaunchKernelGGL(k_finalize, dim3(1), dim3(BLOCK), 0, s, partials, G, nq, maxmask, red_dev);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(s));
+    for (int k = 0; k < nvec[kernel]; ++k)
+        if (vout[k]) HIPCK(hipMemcpy(vout[k], d[k], sizeof(double) * len[k], hipMemcpyDeviceToHost));
+    if (nq > 0) {
+        HIPCK(hipMemcpy(red, red_dev, sizeof(double) * nq, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(part_out, partials, sizeof(double) * (size_t)nq * G, hipMemcpyDeviceToHost));
+    }
+    if (pub_dev) HIPCK(hipMemcpy(pub, pub_dev, sizeof(double), hipMemcpyDeviceToHost));
+    grid[0] = G; grid[1] = nq;
+    return FASP_SUCCESS;
+}
+
 // CPU test entry: the sliced-ELL coding of A as upload_csr would build it (device_csr.hip.h, build_sell), decoded again and walked on the host
 int fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double* bytes, int* ia_out, int* ja_out, double* val_out, const double* x, double* y)
 {

@@ -150,6 +150,50 @@ int fasp_hip_tune(const char* key, int value);
  * [2 ..] the fused form's scalars, [10 ..] the sequence's.  Maxima skip NaN entries (fmax).  The fused forms of 0, 2 and 5 write the
  * iterate out of place.  < 0: error (no device: ERROR_MISC). */
 int fasp_hip_safe_update_selftest(int which, int n, int seed, double* out);
+/* test entry: ONE launch of one of the small kernels between the matrix products (the BLAS-1 part of csrc/kernels.hip.h, k_pack of
+ * csrc/hierarchy.hip.h) on the caller's inputs, with the grid rule and the context buffers of the kernel's production call site, followed
+ * by k_finalize where the solvers follow it with one.  The entry holds no reference and generates no input.
+ *   vin   6 host pointers, the kernel's vectors by slot (below), n doubles each unless said otherwise; the slots the kernel has must be set
+ *   vout  6 host pointers or NULL each: slot k of the device, as the kernel left it, is copied there (same length as vin[k])
+ *   scal  8 doubles, ipar 4 ints: the kernel's scalars (below)
+ *   part_in, npart   per-block partials a folded variant sums itself (1 <= npart <= 2048, the partial buffer's width per quantity; else
+ *         npart = 0); k_finalize: its nq * G inputs, quantity by quantity
+ *   red   8 doubles: what k_finalize made of the kernel's partials ([0 .. grid[1]))
+ *   part_out  8 * 2048 doubles: the kernel's raw partials, part_out[q * grid[0] + block]
+ *   grid  2 ints: [0] the workgroups launched, [1] the number of reduced quantities (0: the kernel reduces nothing)
+ *   pub   1 double: the scalar the kernel publishes or divides by, read back from its device slot, which held NaN before the launch
+ *         unless an unfolded variant's input was put there (k_cg_update: (t,p); k_axpby_beta: the numerator; k_mgs_step: h)
+ *   kernel            variant                                     vectors by slot                 scal              grid, reduction
+ *    0 k_cg_update    bit 0: (t,p) summed from part_in, else      p, t, u, r, zx, zdiag           temp1, (t,p),     vec_grid(n); r.r, with bit 2
+ *                     scal[1] in slot 8 of d_red; bit 1: temp1                                    zomega,           also u.u, p.p, max|u|, #NaN(u)
+ *                     read from slot 12 of d_red (the kernel's                                    zdiag_value       (maxmask 8)
+ *                     own temp1 argument is then NaN); bit 2:
+ *                     full_norms; bit 3: zx with the zdiag array;
+ *                     bit 4: zx with zdiag_value (not both)
+ *    1 k_axpby_beta   bit 0: numerator summed from part_in        x, y                            num, den          vec_grid(n / 2 + 1)
+ *    2 k_mgs_step     bit 0: h summed from part_in; bit 1: pnext  pj, pi, pnext                   h                 vec_grid(n); (pnext or pi, pi)
+ *    3 k_finalize     --  (n = G <= 2048, npart = nq * G)         --                              ipar: nq, maxmask one workgroup; nq quantities
+ *    4 k_dot          --                                          x, y                            --                vec_grid(n); x.y
+ *    5 k_norms        --                                          x                               --                vec_grid(n); x.x, max|x| (maxmask 2)
+ *    6 k_norm1_nan    --                                          x                               --                vec_grid(n); sum|x|, #NaN(x)
+ *    7 k_axpy         --                                          x, y                            a                 vec_grid(n / 2 + 1)
+ *    8 k_axpby        --                                          x, y                            a, b              vec_grid(n / 2 + 1)
+ *    9 k_axpyz        0: z apart; 1: z is x; 2: z is y            x, y, z                         a                 vec_grid(n)
+ *   10 k_axpy_self    --                                          y                               a                 vec_grid(n)
+ *   11 k_scale        --                                          x                               a                 vec_grid(n)
+ *   12 k_set          --                                          x                               v                 vec_grid(n)
+ *   13 k_poly_scale   --                                          dinv, r, rbar                   --                vec_grid(n)
+ *   14 k_poly_start   --                                          dinv, rbar, v0, v1              k1, k2, k3        vec_grid(n)
+ *   15 k_poly_step    --                                          dinv, r, rbar, v0, v1, vnew     k4, k5            vec_grid(n)
+ *   16 k_jacobi_zero  --                                          b, d, x                         w                 vec_grid(n)
+ *   17 k_l1_zero      --                                          b, d, x                         --                vec_grid(n)
+ *   18 k_diag_precond --                                          d, r, z                         --                vec_grid(n)
+ *   19 k_bsr_dinv_apply  --  (n scalar rows, a multiple of nb)    dinv (n * nb doubles), b, u     ipar: nb          vec_grid(n)
+ *   20 k_pack         --  (n = nsend; idx: n ints in [0, nv))     v (nv doubles), out             ipar: nv          vec_grid(n)
+ * Returns FASP_SUCCESS; ERROR_INPUT_PAR for a NULL argument, an unknown kernel or variant, n < 1 or > 2^30, a missing vector, an index outside v, or
+ * an npart the partial buffer does not hold (nothing is launched); ERROR_MISC without a device (nothing is written). */
+int fasp_hip_blas1_op(int kernel, int variant, int n, const int* ipar, const double* scal, const double* const* vin, double* const* vout,
+                      const double* part_in, int npart, const int* idx, double* red, double* part_out, int* grid, double* pub);
 /* measurement entry (tools/perf_safe_krylov.py): wall seconds the last Krylov solve of this process with a caller's `precond` (the
  * fasp_solver_d{csr,bsr,str}_p* / _sp* entries and the matrix-free ones) spent in its iteration, from the first residual to the
  * synchronise behind the last one; the upload of the operator, the binding of the preconditioner and the copy of x are outside. */
