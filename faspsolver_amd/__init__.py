@@ -53,7 +53,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_param_ilu_init", "fasp_ilu_data_create", "fasp_ilu_data_free", "fasp_mem_iludata_check", "fasp_ilu_dcsr_setup",
     "fasp_precond_ilu", "fasp_precond_ilu_forward", "fasp_precond_ilu_backward", "fasp_solver_dcsr_krylov_ilu",
     "fasp_solver_dcsr_krylov_ilu_M", "fasp_smoother_dcsr_ilu", "fasp_fwrapper_dcsr_krylov_ilu_",
-    "fasp_hip_ilu_resident_count", "fasp_hip_ilu_time",
+    "fasp_hip_ilu_resident_count", "fasp_hip_ilu_time", "fasp_hip_ilu_schedule",
     "fasp_ilu_dbsr_setup", "fasp_precond_dbsr_ilu", "fasp_solver_dbsr_krylov_ilu", "fasp_smoother_dbsr_ilu",
     "fasp_fwrapper_dbsr_krylov_ilu_",
     "fasp_hip_bsr_amg_get_ilu", "fasp_hip_bsr_amg_ilu_info", "fasp_hip_bsr_amg_ilu_smooth_time",
@@ -286,6 +286,7 @@ def lib():
     L.fasp_fwrapper_dcsr_krylov_ilu_.restype = None
     L.fasp_hip_ilu_time.argtypes = [P(T.ILU_data), C.c_int, C.c_int, T.c_double_p]
     L.fasp_hip_ilu_time.restype = C.c_double
+    L.fasp_hip_ilu_schedule.argtypes = [P(T.ILU_data), C.c_int, C.c_int, T.c_double_p]
     # block ILU (csrc/ilu_setup.cpp, csrc/ilu.hip.h)
     L.fasp_ilu_dbsr_setup.argtypes = [P(T.dBSRmat), P(T.ILU_data), P(T.ILU_param)]
     L.fasp_ilu_dbsr_setup.restype = C.c_short

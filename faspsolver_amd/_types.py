@@ -17,6 +17,7 @@ ERROR_INPUT_PAR = -13
 ERROR_NUM_BLOCKS = -18
 ERROR_MISC = -19
 ERROR_ALLOC_MEM = -20
+ERROR_DATA_STRUCTURE = -21
 ERROR_AMG_INTERP_TYPE = -30
 ERROR_AMG_SMOOTH_TYPE = -31
 ERROR_AMG_COARSE_TYPE = -32

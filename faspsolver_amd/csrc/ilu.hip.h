@@ -20,7 +20,9 @@
 //                    (the data is the flag: cdna_hip_programming.md Guideline 16, R2), read by agent-scope loads that spin
 //                    while they see the sentinel.  A chunk only waits for rows of lower levels, which hold lower tickets,
 //                    drawn by wavefronts that are running: no residency assumption.  Spins are bounded (flow_give_up: 2 s,
-//                    then the error word, the solve fails loudly and later solves use level launches).
+//                    then the error word, the solve fails loudly and later solves use level launches).  Known limit: a value
+//                    whose bits are all set (a NaN with that payload, in the right-hand side or computed) is the sentinel
+//                    itself, so a reader of it waits until flow_give_up; the default quiet NaN and infinities are not.
 // The form follows the schedule's depth (single launch beyond ILU_FLOW_MIN_LEVELS levels); fasp_hip_tune("ilu_form", 0 / 1)
 // forces one.  ILU(0) of P7(n) has 3 n - 2 levels per triangle: 766 at 256^3.
 //
@@ -306,19 +308,26 @@ IluDev* ilu_upload(const ILU_data* d, int nb, int* st)
     return D;
 }
 
+// the form the schedule's depth asks for when nothing forces one
+bool ilu_auto_single(const IluTri& T) { return T.nlev > ILU_FLOW_MIN_LEVELS; }
+
 bool ilu_single_launch(const IluTri& T)
 {
     if (g_tune.ilu_form == 0 || g_flow_disabled) return false;
     if (g_tune.ilu_form == 1) return true;
-    return T.nlev > ILU_FLOW_MIN_LEVELS;
+    return ilu_auto_single(T);
 }
+
+// workgroups (four wavefronts, one chunk each) of the launch of chunks [c0, c1) of one level, and of the single launch
+int ilu_level_grid(int c0, int c1) { return (c1 - c0 + 3) / 4; }
+int ilu_flow_grid(const IluTri& T) { return std::max(1, std::min((T.nchunk + 3) / 4, 1024)); }
 
 template <int NB>
 void ilu_launch(const IluTri& T, bool upper, bool single, const IluArgs& a)
 {
     const bool epi = upper && a.x != nullptr;
     if (single) {
-        const int grid = std::max(1, std::min((T.nchunk + 3) / 4, 1024));
+        const int grid = ilu_flow_grid(T);
         if (epi) hipLaunchKernelGGL((k_ilu_flow<NB, true, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
         else if (upper) hipLaunchKernelGGL((k_ilu_flow<NB, true>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
         else hipLaunchKernelGGL((k_ilu_flow<NB, false>), dim3(grid), dim3(256), 0, g_ctx.stream, a);
@@ -326,7 +335,7 @@ void ilu_launch(const IluTri& T, bool upper, bool single, const IluArgs& a)
     }
     for (int l = 0; l < T.nlev; ++l) {
         const int c0 = T.lvl_chunk[(size_t)l], c1 = T.lvl_chunk[(size_t)l + 1];
-        const dim3 grid((unsigned)((c1 - c0 + 3) / 4));
+        const dim3 grid((unsigned)ilu_level_grid(c0, c1));
         if (epi) hipLaunchKernelGGL((k_ilu_level<NB, true, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
         else if (upper) hipLaunchKernelGGL((k_ilu_level<NB, true>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
         else hipLaunchKernelGGL((k_ilu_level<NB, false>), grid, dim3(256), 0, g_ctx.stream, a, c0, c1);
@@ -610,6 +619,26 @@ int fasp_hip_ilu_resident_count(void)
     int c = 0;
     for (const IluEntry& e : g_ilu_registry) c += e.dev ? 1 : 0;
     return c;
+}
+
+// test entry (fasp_hip_dev.h): the schedule of one triangle (which: 1 L, 2 U) of a factor applied with nb x nb blocks, from a
+// device copy made and freed here; nothing is launched.  info = {levels, chunks, slab entries, actual entries, longest row,
+// single launch by the depth rule (whatever ilu_form forces), workgroups of the level launches summed, of the single launch}
+int fasp_hip_ilu_schedule(ILU_data* iludata, int nb, int which, double info[8])
+{
+    FASP_ENTRY();
+    if (!info) return ERROR_INPUT_PAR;
+    for (int i = 0; i < 8; ++i) info[i] = 0.0;
+    if (which != 1 && which != 2) return ERROR_INPUT_PAR;
+    int st;
+    std::unique_ptr<IluDev, void (*)(IluDev*)> D(ilu_upload(iludata, nb, &st), ilu_dev_destroy);
+    if (!D) return st;
+    const IluTri& T = which == 1 ? D->L : D->U;
+    long long wgs = 0;
+    for (int l = 0; l < T.nlev; ++l) wgs += ilu_level_grid(T.lvl_chunk[(size_t)l], T.lvl_chunk[(size_t)l + 1]);
+    info[0] = T.nlev; info[1] = T.nchunk; info[2] = (double)T.nent; info[3] = (double)T.nreal; info[4] = T.maxlen;
+    info[5] = ilu_auto_single(T) ? 1 : 0; info[6] = (double)wgs; info[7] = ilu_flow_grid(T);
+    return FASP_SUCCESS;
 }
 
 // measurement entry (fasp_hip_dev.h): microseconds per solve of one triangle of a factor (which: 1 L, 2 U), the factor kept

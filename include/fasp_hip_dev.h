@@ -47,9 +47,16 @@ int fasp_hip_measure_ceilings(double* out, size_t bytes, int reps);
  * of one triangle (which: 1 = L, 2 = U) on the device copy, averaged over `reps` back-to-back solves after one warm-up; info
  * (may be NULL, 6 doubles) = {dependency levels, form (1 single launch, 0 level launches), bytes moved per solve, slab
  * entries (padded), entries, longest row}; < 0: error.  A factor of fasp_ilu_dbsr_setup is timed as the block factor it
- * is (the registry's record), its bytes counted from the block layout. */
+ * is (the registry's record), its bytes counted from the block layout.  fasp_hip_ilu_schedule: the schedule of one triangle
+ * (which: 1 = L, 2 = U) of any factor in the MSR layout, applied with nb x nb blocks (1..7), from a device copy made and freed by
+ * the call -- nothing is launched, nothing becomes resident; info = {dependency levels, chunks of 64 rows, slab entries (padded),
+ * entries, longest row, 1 if the depth alone selects the single launch (fasp_hip_tune("ilu_form", ..) is not consulted),
+ * workgroups of the level launches summed over the levels, workgroups of the single launch}.  Returns 0, ERROR_INPUT_PAR (NULL
+ * arguments, row <= 0, nb outside 1..7, another `which`), ERROR_DATA_STRUCTURE (a column index outside [0, row) among the entries
+ * a triangle reads), ERROR_MISC (no device), ERROR_ALLOC_MEM; info is zeroed on every error. */
 int    fasp_hip_ilu_resident_count(void);
 double fasp_hip_ilu_time(ILU_data* iludata, int which, int reps, double* info);
+int    fasp_hip_ilu_schedule(ILU_data* iludata, int nb, int which, double info[8]);
 /* ILU smoothing in the block AMG cycle (AMG_param.ILU_levels > 0 with a BSR hierarchy).  The factors belong to the hierarchy:
  * they are not among fasp_hip_ilu_resident_count's.  fasp_hip_bsr_amg_get_ilu: *view = the host factor of `level` (borrowed:
  * valid until the hierarchy is destroyed, not to be freed); returns 1, or 0 when the level has none (at or beyond ILU_levels,

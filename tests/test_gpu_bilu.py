@@ -3,7 +3,8 @@
      registered (resident) factor and with a caller-built copy of it; fasp_smoother_dbsr_ilu likewise;
   2. SPE01 with fasp_solver_dbsr_krylov_ilu, every BSR Krylov method x ILU(0) / ILU(1): the reference's iteration counts
      (the tutorial case pinned: GMRES, tol 1e-6, ILU(0): 18); CG + ILU(0) on SPD P7(n) (x) B3;
-  3. the Fortran wrapper, residency of factors (block and scalar ones side by side), and the scale P7(64 / 128) (x) B3."""
+  3. the Fortran wrapper, residency of factors (block and scalar ones side by side), and the scale P7(64 / 128) (x) B3.
+Schedule edges and hand-built factors: see test_gpu_ilu_kernels.py."""
 import ctypes as C
 
 import numpy as np

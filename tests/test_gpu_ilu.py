@@ -6,7 +6,8 @@
   3. every Krylov method of fasp_solver_dcsr_itsolver with ILU(0) and ILUt on FE and P7(24): the reference's iteration
      counts, final residuals to the usual rule (BiCGstab / MinRes on FE: to 1e-3, see the test);
   4. fasp_precond_setup(PREC_ILU) + fasp_solver_dcsr_pcg, twenty rounds, no device factor left behind;
-  5. ILU-CG at P7(64) / P7(128)."""
+  5. ILU-CG at P7(64) / P7(128).
+Schedule edges and hand-built factors: see test_gpu_ilu_kernels.py."""
 import ctypes as C
 
 import numpy as np
