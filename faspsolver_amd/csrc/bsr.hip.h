@@ -249,6 +249,23 @@ static int bsr_halo(BsrLevel& Lv, double* v)
     return st;
 }
 
+// The coarse GMRES of the block path, decided once (fasp_hip_bsr_coarse_plan shows it to the CPU): family 8 k_gmres_small<SmallBSR, LV>
+// (LV: the basis in LDS; cache2: the rows beyond the first 512 of an nb = 3 system keep their blocks in LDS behind the basis) while the
+// level fits one CU's caches, else 9, gmres_device.  n = ROW nb scalar rows, NNZ blocks.
+struct BsrCoarsePlan { int family = 9, LV = 0, cache2 = 0, lds = 0, threads = 0, blocks = 1; };   // (threads 0: gmres_device launches its own kernels)
+static BsrCoarsePlan plan_coarse_bsr(int nb, int ROW, int NNZ, bool small_coarse, const Tuning& tune)
+{
+    BsrCoarsePlan p;
+    const int n = ROW * nb;
+    if (!(small_coarse && (long long)ROW * nb <= 4096 && (long long)NNZ * nb * nb <= 131072)) return p;
+    p.family = 8; p.threads = SMALL_BLOCK;
+    size_t lds = sizeof(double) * (size_t)(25 + 2) * (size_t)n;
+    const size_t lds2 = (size_t)std::max(n - SMALL_BLOCK, 0) * GM_CB * 28;
+    if (nb == 3 && n <= 2 * SMALL_BLOCK && lds + lds2 <= 140 * 1024) { p.cache2 = 1; lds += lds2; }
+    if (tune.small_lds && lds <= 140 * 1024) { p.LV = 1; p.lds = (int)lds; }
+    return p;
+}
+
 // fasp_solver_mgcycle_bsr, PreMGCycle.c:287-566
 static int mgcycle_bsr(fasp_hip_amg_bsr* h, const AMG_param& param)
 {
@@ -292,37 +309,30 @@ ForwardSweep:
         const double ctol = param.tol, atol = ctol * 1e-8;
         int st;
         const TmpBSR& Ac = *Lc.A;
-        if (small_coarse_ok(csize, (long long)Ac.NNZ * Ac.nb * Ac.nb)) {
+        const BsrCoarsePlan plan = plan_coarse_bsr(Ac.nb, Ac.ROW, Ac.NNZ, small_coarse_enabled(), g_tune);
+        report_coarse_plan(h->coarse_kinfo, plan.family, plan.LV, plan.cache2);
+        if (plan.family == 8) {
             if (!h->small_ws) HIPCK(hipMalloc(&h->small_ws, sizeof(double) * (size_t)(25 + 2) * std::max(csize, 1)));
             GmresArgs<SmallBSR> a{};
             a.A = SmallBSR{Ac.ROW, Ac.nb, Ac.ia, Ac.ja, Ac.val};
             a.b = Lc.b; a.x = Lc.x; a.ws = h->small_ws; a.tol = ctol; a.abstol = atol;
-            a.MaxIt = cmaxit; a.restart = 25; a.out = small_out_dev();
-            size_t lds = sizeof(double) * (size_t)(25 + 2) * (size_t)csize;
-            // rows beyond the first 512 of an nb = 3 system keep their blocks in LDS behind the basis (k_gmres_small)
-            const size_t lds2 = (size_t)std::max(csize - SMALL_BLOCK, 0) * GM_CB * 28;
-            if (Ac.nb == 3 && csize <= 2 * SMALL_BLOCK && lds + lds2 <= 140 * 1024) { a.cache2 = 1; lds += lds2; }
-            static bool attr = false;
-            if (!attr) {
-                (void)hipFuncSetAttribute((const void*)k_gmres_small<SmallBSR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                attr = true;
-            }
-            if (g_tune.small_lds && lds <= 140 * 1024)
-                hipLaunchKernelGGL((k_gmres_small<SmallBSR, true>), dim3(1), dim3(SMALL_BLOCK), lds, s, a);
-            else
-                hipLaunchKernelGGL((k_gmres_small<SmallBSR, false>), dim3(1), dim3(SMALL_BLOCK), 0, s, a);
+            a.MaxIt = cmaxit; a.restart = 25; a.out = small_out_dev(); a.cache2 = plan.cache2;
+            if (plan.LV) {
+                (void)allow_lds<k_gmres_small<SmallBSR, true>>(COARSE_LDS_OPT);
+                hipLaunchKernelGGL((k_gmres_small<SmallBSR, true>), dim3(1), dim3(plan.threads), (size_t)plan.lds, s, a);
+            } else
+                hipLaunchKernelGGL((k_gmres_small<SmallBSR, false>), dim3(1), dim3(plan.threads), 0, s, a);
             SmallOut o;
             if (small_out_fetch(o) < 0) return ERROR_MISC;
             st = o.status;
             h->coarse_iters += o.iters;
-            h->coarse_kinfo[0] = 8; h->coarse_kinfo[1] = (g_tune.small_lds && lds <= 140 * 1024) ? 1 : 0; h->coarse_kinfo[2] = a.cache2;
             h->coarse_kinfo[3] = o.status; h->coarse_kinfo[4] = o.iters;
         } else {
             KOps K = bsr_ops(h, nl - 1, 1);
             PcgOut po{BIGREAL, BIGREAL, BIGREAL};
             st = gmres_device(K, Lc.b, Lc.x, 0, ctol, atol, cmaxit, 25, STOP_REL_RES, 0, nullptr, &po);
             if (st >= 0) h->coarse_iters += st;
-            h->coarse_kinfo[0] = 9; h->coarse_kinfo[1] = 0; h->coarse_kinfo[2] = 0; h->coarse_kinfo[3] = st; h->coarse_kinfo[4] = std::max(st, 0);
+            h->coarse_kinfo[3] = st; h->coarse_kinfo[4] = std::max(st, 0);
         }
         if (st < 0 && st != ERROR_SOLVER_MAXIT && st != ERROR_SOLVER_STAG && st != ERROR_SOLVER_SOLSTAG &&
             st != ERROR_SOLVER_TOLSMALL) return st;  // device failure, not a convergence verdict

@@ -14,9 +14,7 @@ static int coarse_solve(fasp_hip_amg* h, const AMG_param& param, double tol)
     if (st == ERROR_MISC) return st;  // device failure, not a solver verdict
     if (st < 0) {
         // safety net of PreMGUtil.inl:50-52: fasp_solver_dcsr_spvgmres(A, b, x, NULL, ctol, maxit, 20, 1, ..)
-        const int m = Lc.A.row;
-        const int nn = (int)((unsigned)m * (unsigned)m);
-        const int maxit = std::max(250, std::min(nn, 1000));
+        const int maxit = coarse_maxit(Lc.A.row);
         KOps Kc = csr_ops(h, nl - 1, false);
         st = gmres_device(Kc, Lc.b, Lc.x, 2, tol, 0.0, maxit, 20, STOP_REL_RES, param.print_level - 4,
                           nullptr, nullptr);
@@ -436,7 +434,7 @@ static int precond_amg(fasp_hip_amg* h, double* r, double** z)
     // cycle only reads -- with the verdicts read as they come, and the hierarchy stays in that mode.
     const DevLevel& Dc = h->L.back();
     // (not for full multigrid: its cycle carries the levels' iterates over from one application to the next, a replay would not start where the first attempt did)
-    const bool lazy = g_tune.lazy_coarse && !h->coarse_sync && !h->use_fmg && h->L.size() > 1 && small_coarse_ok(Dc.A.row, Dc.A.nnz);
+    const bool lazy = g_tune.lazy_coarse && !h->coarse_sync && !h->use_fmg && h->L.size() > 1 && coarse_plan(h, Dc).lazy;
     if (lazy && !h->d_lazy) {
         HIPCK(hipMalloc((void**)&h->d_lazy, 2 * sizeof(int)));
         HIPCK(hipHostMalloc((void**)&h->h_lazy, 4 * sizeof(int), hipHostMallocDefault));

@@ -85,6 +85,21 @@ using namespace fasp;
 // a sweep schedule under construction on a host thread of its own (smoothers.hip.h, sched_jobs_start)
 struct SchedJob { int level = 0, kind = 0, st = 0; bool uploaded = false; SplitHost H; DevLevel::Sched S; std::thread th; };   // S: the schedule on the device, uploaded by the job's own thread
 
+// The plan of the coarsest level's safe CG (coarse_cg.hip.h: plan_coarse_spcg decides, the launchers execute, mgcycle and the reports read).
+// family = the codes of fasp_hip_coarse_kernel_info, p1 / p2 its two parameters: 1 k_spcg_dpp (NBK, sends ahead), 2 k_spcg_reg (MC, 0),
+// 3 k_spcg_wave, 4 k_spcg_small (LDS level: 2 vectors + matrix, 1 vectors, 0 none), 5 k_spcg_fused (E, 0), 6 k_spcg_persist (NE, u in LDS),
+// 7 launch_csr<OP_MXV_DOT> + k_spcg_step_reg (E, 0) / k_spcg_step (0, 0).  threads / blocks / lds: the launch of that kernel (family 7: of
+// the step kernel).  The order of the first eleven ints is fasp_hip_coarse_plan's layout (fasp_hip_dev.h).
+struct CoarsePlan {
+    int family = 0, p1 = 0, p2 = 0;
+    int threads = 0, blocks = 0, lds = 0;
+    int LD = 0;          // families 1 .. 3: row stride of the dense image in doubles (conflict-free lane = row reads)
+    int MaxIt = 0;
+    int lazy = 0;        // one launch per solve that leaves its verdict on the device: it may be read once per application (precond_amg)
+    int dev_start = 0;   // the start of the solve runs on the device (k_spcg_init)
+    int batch = 0;       // families 5, 7: iterations queued between two waits
+};
+
 struct fasp_hip_amg {
     // brick renumbering (upload_level): perm[l][k] = natural index of the row that level l's device copy numbers k (empty: natural order)
     std::vector<std::vector<int>> perm;
@@ -110,8 +125,9 @@ struct fasp_hip_amg {
     double*              spcg_fused_buf = nullptr;  // second parity of r, p, t and the broadcast record (k_spcg_fused)
     int                  spcg_last_iters = 0;   // iterations of the previous coarse solve: sizes the first batch of the next one
     SpcgState*           spcg_state = nullptr;  // device-resident state of the batched coarse CG
-    // k_spcg_persist: the coarsest matrix dealt to the waves of the chip (built on first use; tried == true afterwards)
-    struct Persist { bool tried = false, ok = false; int NE = 0, nblocks = 0; double* vals = nullptr; unsigned short* cols = nullptr;
+    CoarsePlan           cplan; unsigned cplan_gen = 0;   // remade when g_coarse_gen moved on (a tune key, the persistent kernel's fallback)
+    // k_spcg_persist: the coarsest matrix dealt to the waves of the chip, on the device (NE == 0: not uploaded; failed: no memory for it)
+    struct Persist { bool failed = false; int NE = 0; double* vals = nullptr; unsigned short* cols = nullptr;
                      int *wrow = nullptr, *wend = nullptr; double* t2 = nullptr; unsigned* sync = nullptr; unsigned launches = 0; } persist;
     std::vector<double>  amli_coef;             // AMLI polynomial coefficients (amli_degree + 1), formed on first use
     std::vector<int>     level_cycle_type;      // AMG_data.cycle_type per level as the setup leaves it (K-cycle)
@@ -125,7 +141,7 @@ struct fasp_hip_amg {
     // lazy coarse verdicts (precond_amg): device words {min status, iteration sum}, their pinned host copy; coarse_sync: a coarse
     // solve gave up once on this hierarchy -- verdicts are read per solve from then on
     int*                   d_lazy = nullptr; int* h_lazy = nullptr; bool lazy_active = false, coarse_sync = false;
-    double*                reg_img = nullptr; int reg_mc = 0;   // k_spcg_reg: the coarsest matrix as its threads hold it
+    double*                reg_img = nullptr; int reg_img_family = 0, reg_img_par = 0;   // the coarsest matrix as the threads of k_spcg_dpp<NBK> (1, NBK) / k_spcg_reg<MC> (2, MC) hold it
     double                 upload_seconds = 0.0;
 };
 

@@ -2369,6 +2369,7 @@ int fasp_hip_tune(const char* key, int value)
 {
     FASP_ENTRY();
     if (!key) return ERROR_INPUT_PAR;
+    ++g_coarse_gen;   // the coarse plans kept on the handles are remade (coarse_cg.hip.h)
     if (!std::strcmp(key, "maxgrid")) g_tune.maxgrid = value;
     else if (!std::strcmp(key, "xcd")) g_tune.xcd = value;
     else if (!std::strcmp(key, "gen2")) g_tune.gen2 = value;
@@ -2711,6 +2712,30 @@ int fasp_hip_csr_plan(const int* traits, int op, int windowed, int want_partials
     const int out[11] = {(int)p.kernel, p.family, p.tile_rows, p.bpc, p.xcd_map, p.tpp, p.nt, p.ja16, p.jbase, p.fused_zr, kernel_family(M, nullptr)};
     std::copy(out, out + 11, plan);
     if (bytes) *bytes = p.bytes;
+    return FASP_SUCCESS;
+}
+
+// CPU test entries: plan_coarse_spcg (coarse_cg.hip.h) and plan_coarse_bsr (bsr.hip.h) under the tune keys in force (fasp_hip_dev.h has the layouts)
+int fasp_hip_coarse_plan(int m, int nnz, const int* ia, int plain_csr, int num_cu, int* plan_out)
+{
+    FASP_ENTRY();
+    if (m < 1 || nnz < 0 || !plan_out) return ERROR_INPUT_PAR;
+    CoarseTraits c;
+    c.m = m; c.nnz = nnz; c.ia = ia; c.plain_csr = plain_csr != 0; c.num_cu = num_cu;
+    c.shared_device = comm_shares_devices(); c.persist_off = g_persist_disabled; c.small_coarse = small_coarse_enabled();
+    const CoarsePlan p = plan_coarse_spcg(c, g_tune, nullptr);
+    const int out[11] = {p.family, p.p1, p.p2, p.threads, p.blocks, p.lds, p.LD, p.MaxIt, p.lazy, p.dev_start, p.batch};
+    std::copy(out, out + 11, plan_out);
+    return FASP_SUCCESS;
+}
+
+int fasp_hip_bsr_coarse_plan(int nb, int ROW, int NNZ, int* plan_out)
+{
+    FASP_ENTRY();
+    if (nb < 1 || ROW < 1 || NNZ < 0 || (long long)ROW * nb > 0x7fffffff || !plan_out) return ERROR_INPUT_PAR;
+    const BsrCoarsePlan p = plan_coarse_bsr(nb, ROW, NNZ, small_coarse_enabled(), g_tune);
+    const int out[6] = {p.family, p.LV, p.cache2, p.lds, p.threads, p.blocks};
+    std::copy(out, out + 6, plan_out);
     return FASP_SUCCESS;
 }
 

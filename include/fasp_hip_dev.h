@@ -255,6 +255,22 @@ int  fasp_hip_estream_selftest(const int* ia, int nrow, int nnz, int per_wave, i
  * passed, jbase passed, the launch writes the fused (x_new, b) partials of a Jacobi sweep, the family fasp_hip_amg_kernel_info reports for the
  * operator (that of op 0 on the whole operator)}; *bytes (may be NULL) = matrix bytes of one pass. */
 int  fasp_hip_csr_plan(const int* traits, int op, int windowed, int want_partials, int* plan, double* bytes);
+/* The plan of the coarsest level's safe CG (csrc/coarse_cg.hip.h, plan_coarse_spcg: the function coarse_spcg's launchers execute, the cycle and
+ * fasp_hip_coarse_kernel_info read) for a level of m rows and nnz stored entries, under the tune keys in force and the FASP_HIP_SMALL_COARSE
+ * switch.  No GPU needed.  ia: the level's row pointer (m + 1 ints), read for the deal of k_spcg_persist only; NULL: that form counts as refused.
+ * plain_csr: the device operator is usable as plain CSR (no lossless coding took its values and columns); num_cu: compute units of the chip.
+ * plan_out (11 ints) = {family, p1, p2 -- the triple fasp_hip_coarse_kernel_info reports once the kernels ran: 1 k_spcg_dpp (NBK, direction sent
+ * ahead), 2 k_spcg_reg (MC, 0), 3 k_spcg_wave, 4 k_spcg_small (LDS level: 2 vectors and matrix, 1 vectors, 0 none), 5 k_spcg_fused (E, 0),
+ * 6 k_spcg_persist (NE, u in LDS), 7 launch_csr<OP_MXV_DOT> + k_spcg_step_reg (E, 0) / k_spcg_step (0, 0) --, threads per block, blocks, dynamic
+ * LDS bytes (family 7: of the step kernel), LD (row stride of the dense image in doubles; families 1 .. 3, else 0), MaxIt = max(250, min(m^2,
+ * 1000)), the verdict may be read lazily (once per application of the preconditioner), the start of the solve runs on the device
+ * (k_spcg_init), iterations queued between two waits of the host (families 5, 7; else 0)}. */
+int  fasp_hip_coarse_plan(int m, int nnz, const int* ia, int plain_csr, int num_cu, int* plan_out);
+/* ... and of the block path's coarse GMRES (csrc/bsr.hip.h, plan_coarse_bsr; mgcycle_bsr launches from it) for ROW block rows of nb x nb blocks,
+ * NNZ blocks: plan_out (6 ints) = {family -- 8 k_gmres_small<SmallBSR, LV>, 9 gmres_device --, LV (the basis in LDS), cache2 (nb = 3: the rows
+ * beyond the first 512 keep their blocks in LDS behind the basis), dynamic LDS bytes, threads per block (0 for family 9, whose kernels have
+ * launches of their own), blocks}. */
+int  fasp_hip_bsr_coarse_plan(int nb, int ROW, int NNZ, int* plan_out);
 /* The value-indexed sliced-ELL coding of k_csr_sell (csrc/kernels4.hip.h) built on the HOST as an upload would build it.  cap_percent: largest
  * slots / entries accepted, in percent (<= 0: the product's 125).  info[8] = {coded (1 / 0), why not (0 coded, 1 size or mean row length outside the
  * range served, 2 a row beyond 255 entries, 3 padding over the cap, 4 too many distinct values, 5 index + offset beyond 32 bits), distinct values,
