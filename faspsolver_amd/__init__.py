@@ -86,7 +86,7 @@ EXPORTS = [  # every symbol include/fasp_hip.h declares
     "fasp_solver_dcsr_itsolver_s", "fasp_solver_dcsr_krylov_s", "fasp_solver_dbsr_spbcgs", "fasp_solver_dbsr_spgmres",
     "fasp_solver_dbsr_spvgmres", "fasp_solver_dstr_spcg", "fasp_solver_dstr_spbcgs", "fasp_solver_dstr_spminres",
     "fasp_solver_dstr_spgmres", "fasp_solver_dstr_spvgmres", "fasp_hip_safe_update_selftest", "fasp_hip_plugin_solve_seconds",
-    "fasp_hip_blas1_op",
+    "fasp_hip_blas1_op", "fasp_hip_level_smooth",
 ]
 SAFE_METHODS = ("spcg", "spbcgs", "spminres", "spgmres", "spvgmres")   # the safe-net Krylov methods (KrySP*.c) ...
 SAFE_FORMATS = {"csr": SAFE_METHODS, "bsr": ("spbcgs", "spgmres", "spvgmres"), "str": SAFE_METHODS}   # ... the reference has per format
@@ -215,6 +215,8 @@ def lib():
     L.fasp_hip_amg_num_levels.argtypes = [C.c_void_p]
     L.fasp_hip_amg_get_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, P(T.dCSRmat)]
     L.fasp_hip_amg_get_cfmark.argtypes = [C.c_void_p, C.c_int, P(T.ivector)]
+    L.fasp_hip_level_smooth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                        T.c_double_p, T.c_double_p]
     L.fasp_hip_solve.argtypes = [C.c_void_p, P(T.dvector), P(T.dvector), P(T.ITS_param),
                                  T.c_double_p, C.c_int, P(T.fasp_hip_stats)]
     L.fasp_hip_set_rhs.argtypes = [C.c_void_p, P(T.dvector)]
@@ -698,6 +700,15 @@ class AMG:
         if st < 0:
             raise RuntimeError(f"fasp_hip_precond_amg failed: {st}")
         return z
+
+    def level_smooth(self, level, post, smoother, order, nsweeps, relax, ndeg, b, x=None):
+        """One smoothing step of a resident level as a cycle takes it (fasp_hip_level_smooth) -> (status, iterate).
+        x None: the step starts from the level's lazily zero iterate, and the buffer handed over is all NaN."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        zero = x is None
+        x = np.full(len(b), np.nan) if zero else np.ascontiguousarray(x, dtype=np.float64).copy()
+        st = lib().fasp_hip_level_smooth(self.h, level, int(post), smoother, order, nsweeps, relax, ndeg, int(zero), T.dp(b), T.dp(x))
+        return st, x
 
     # --- row partition (host side) ---
     def dist_plan(self, rank, nranks, min_rows):

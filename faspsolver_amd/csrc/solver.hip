@@ -2955,6 +2955,40 @@ int fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const doubl
     if (!h || level < 0 || level >= (int)h->L.size()) return ERROR_INPUT_PAR;
     return row_op_host(h->L[level], which, op, x, b, y, y2, scalar, red);
 }
+// Development / test entry: one smoothing step of a resident level through smooth() (smoothers.hip.h), the way a cycle takes it before
+// (post 0) or after (1) the coarse correction, vectors given and returned on the host.  zero_start 1: the step starts from the lazily zero
+// iterate (x_zero), x is not read.  The level's right-hand side pointer and lazy flags are put back; its iterate is overwritten.
+int fasp_hip_level_smooth(fasp_hip_amg* h, int level, int post, int smoother, int order, int nsweeps, double relax, int ndeg, int zero_start,
+                          const double* b, double* x)
+{
+    FASP_ENTRY();
+    if (!h || !b || !x || level < 0 || level >= (int)h->L.size() || h->distributed || (post != 0 && post != 1) ||
+        (zero_start != 0 && zero_start != 1) || nsweeps < 0 || ndeg < 0) return ERROR_INPUT_PAR;
+    DevLevel& D = h->L[level];
+    if (!D.replicated || D.swz || !D.x || !D.xo) return ERROR_INPUT_PAR;
+    const size_t n = (size_t)D.A.row;
+    double* const b0 = D.b;
+    const bool xz0 = D.x_zero, ps0 = D.presmoothed;
+    double* db = nullptr;
+    HIPCK(hipMalloc(&db, sizeof(double) * std::max<size_t>((size_t)D.nvec, 1)));
+    auto run = [&]() -> int {
+        HIPCK(hipMemcpyAsync(db, b, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+        if (!zero_start) HIPCK(hipMemcpyAsync(D.x, x, sizeof(double) * n, hipMemcpyHostToDevice, g_ctx.stream));
+        D.b = db; D.x_zero = zero_start != 0; D.presmoothed = false;
+        const int st = smooth(h, level, post != 0, smoother, order, nsweeps, relax, ndeg);
+        if (st < 0) return st;
+        materialise_zero(D);
+        HIPCK(hipStreamSynchronize(g_ctx.stream));
+        if (seq_err_check() < 0) return ERROR_MISC;
+        HIPCK(hipMemcpy(x, D.x, sizeof(double) * n, hipMemcpyDeviceToHost));
+        return FASP_SUCCESS;
+    };
+    const int st = run();
+    (void)hipStreamSynchronize(g_ctx.stream);
+    D.b = b0; D.x_zero = xz0; D.presmoothed = ps0;
+    (void)hipFree(db);
+    return st;
+}
 // ... and of a matrix given on the host, uploaded the way a level's A is (coding, kernel selection, diagonal tables).  A rectangular matrix is
 // uploaded the way a transfer operator is: no diagonal tables, so ops 5 and 6 return ERROR_INPUT_PAR.  *kind_out: the family code of
 // fasp_hip_amg_kernel_info (kernel_family, device_csr.hip.h: the plan of y = M x on the whole operator).

@@ -283,6 +283,15 @@ int  fasp_hip_sell_selftest(const dCSRmat* A, int cap_percent, int* info, double
  * iterate), 6 L1-diagonal sweep (A only), 7 y = M x fused with (y, b), 8 y = M x with y2_i = scalar y_i / b_i written along (the fused first Jacobi
  * sweep of the next level).  red (may be NULL): the finished fused sum of ops 7 and 5 -- (y, b), (x_new, b); NaN where the kernel has none. */
 int  fasp_hip_level_op(fasp_hip_amg* h, int level, int which, int op, const double* x, const double* b, double* y, double* y2, double scalar, double* red);
+/* test entry: one smoothing step of a resident level as a cycle takes it -- smooth() of csrc/smoothers.hip.h with the arguments of AMG_param
+ * (smoother, smooth_order, sweeps, relaxation, polynomial_degree) -- before (post 0) or after (post 1) the coarse correction; b (right-hand side)
+ * and x (iterate, in and out) are host vectors of the level's row count.  zero_start 1: the step starts from the level's lazily zero iterate and x
+ * is not read.  The level's right-hand side pointer and lazy-iterate flags are left as they were; what the step builds on first use (polynomial
+ * tables, sweep schedules, the C/F marker) stays.  ERROR_INPUT_PAR, nothing touched: no handle / vector, a level that does not exist, is
+ * row-partitioned or a Schwarz level, post or zero_start outside {0, 1}, negative nsweeps or ndeg.  Otherwise smooth()'s status
+ * (ERROR_AMG_SMOOTH_TYPE: an unknown smoother, Jacobi-F / GS-F on a level without C/F marker; x is then left alone). */
+int  fasp_hip_level_smooth(fasp_hip_amg* h, int level, int post, int smoother, int order, int nsweeps, double relax, int ndeg, int zero_start,
+                           const double* b, double* x);
 /* ... and of a matrix given on the host, uploaded the way a level's A is.  *kind_out (may be NULL) = the kernel family that serves y = M x on
  * the whole operator -- whatever `op` is: a Jacobi sweep of an operator without diagonal positions, a smoother on a k_csr_rowpat5 operator and a
  * row window may run on another one (fasp_hip_csr_plan tells) --, in the codes of fasp_hip_amg_kernel_info and from the same plan, evaluated under

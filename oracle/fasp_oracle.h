@@ -117,6 +117,12 @@ void orc_mgcycle(orc_amg* mgl, const AMG_param* param);
 void orc_fmgcycle(orc_amg* mgl, const AMG_param* param);
 /* z = B r with the parameter hand-over of PreCSR.c:416 (tol is NOT forwarded) */
 void orc_precond_amg(orc_amg* mgl, const AMG_param* amgparam, const double* r, double* z);
+/* ... and with the full-multigrid cycle in its place: fasp_precond_famg, PreCSR.c:560 */
+void orc_precond_famg(orc_amg* mgl, const AMG_param* amgparam, const double* r, double* z);
+/* the smoothing step of one level as the cycles take it (PreMGSmoother.inl:49 before, :155 after the coarse correction):
+ * rows 0 .. A->row - 1, ordering = the level's C/F marker (may be NULL) */
+int  orc_smoothing(int post, int smoother, const dCSRmat* A, const double* b, double* x, int nsweeps, double relax,
+                   int order, const int* ordering, int ndeg);
 
 /* Krylov methods.  pc == NULL means no preconditioner.  hist (may be NULL)
  * receives the recurrence residual norms ||r_k||_2 for k = 0..iters (what fasp_itinfo
@@ -163,6 +169,9 @@ void orc_amg_borrow_begin(orc_amg* mgl, int num_levels);
 void orc_amg_borrow_level(orc_amg* mgl, int l, const dCSRmat* A, const dCSRmat* P,
                           const dCSRmat* R, const int* cfmark);
 void orc_amg_borrow_end(orc_amg* mgl);
+/* the AMLI coefficients and the levels' cycle types a setup would have left for param (needed before an AMLI or
+ * K-cycle on a borrowed hierarchy) */
+void orc_amg_borrow_cycles(orc_amg* mgl, const AMG_param* param);
 /* cpu_baseline timing only (bench.py): pin the OpenMP team (thread t -> cpus[t mod n]) / undo it; replace the borrowed
  * level matrices by copies whose pages are first touched by the threads that will read them (static row schedule) --
  * what an OpenMP code on a multi-socket host does.  Arithmetic is untouched. */
